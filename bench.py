@@ -30,7 +30,14 @@ MFMA kernels (ops/x3.py); ``--stock --dtype fp32``: the stock MIOpen / hipBLASLt
 Data is synthetic (ImageNet-shaped 299x299x3 images, random labels) and weights are random-init --
 no network access for datasets / checkpoints.
 
-Usage: python bench.py [--gpus N] [--steps K] [--warmup W] [--batch B] [--ps-mode M] [--dtype D]
+A plain run sets up, runs the W warmup steps, times the K steps and prints the JSON line.  ``--full``
+adds what the headline figure does not need, after the timed steps: the GPU time per step with the host
+far ahead, the phase times of one eager step and the reference-precision ``fp32_row``.
+``--dump-outputs DIR`` writes the last timed step's loss and the BN running statistics it updated as
+``DIR/*.npy``; that step then starts from the seeded initial training state (put back on the GPU right
+before it), so what it computes is the same in every run up to the rounding of the kernels' float atomics.
+
+Usage: python bench.py [--gpus N] [--steps K] [--warmup W] [--batch B] [--ps-mode M] [--dtype D] [--full]
        N>1 under torch.distributed.run (WORLD_SIZE set): one rank per GPU, as the driver launches it;
        N>1 without it: bench.py starts ``python -m torch.distributed.run --nproc-per-node N bench.py ...``
        as a child process (never an exec), relays rank 0's JSON line and exits with the child's code.
@@ -86,9 +93,19 @@ def parse(argv=None):
     ap.add_argument("--collective", default=None, choices=["rccl", "hip"],
                     help="gradient push / pull collectives: RCCL (default) or tony_amd's xGMI peer-memory "
                          "kernels (csrc/xgmi.hip); sets TONY_COLLECTIVE")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also measure what the headline figure does not need: the GPU time "
+                         "per step with the host far ahead, the phase times of one eager step and the "
+                         "reference-precision fp32_row (a plain run sets up, warms up, times the steps and prints)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps write what the last timed step left with its caller as "
+                         "DIR/<name>.npy (float32): the loss and the batch-norm running statistics of every layer.  "
+                         "Batch, initial variables and dropout seed are seeded, and the training state is put back "
+                         "to its initial value right before the last timed step (the clock stops meanwhile), so "
+                         "two runs, or two builds, with the same arguments agree up to the kernels' rounding")
     ap.add_argument("--fp32-row", type=int, default=1,
-                    help="N=1 bf16 runs: also time the reference-precision (x3 fp32) step in a child process and "
-                         "report it as the record's fp32_row (0: skip)")
+                    help="--full, bf16 runs: also time the reference-precision (x3 fp32) step (N=1: in a child "
+                         "process) and report it as the record's fp32_row (0: skip)")
     ap.add_argument("--fp32-steps", type=int, default=10)
     ap.add_argument("--fp32-warmup", type=int, default=3)
     ap.add_argument("--no-miopen-find", action="store_true",
@@ -343,6 +360,7 @@ def main(argv=None):
     # bf16-MFMA products of hi/lo operand planes); --stock: the stock MIOpen / hipBLASLt comparator
     x3 = fp32 and not args.stock and args.model == "inception_v3"
     fused = not (args.stock or fp32)
+    torch.manual_seed(1000 + rank)  # the dropout layers draw their mask seed here: the same in every run
     if args.model == "inception_v3":
         from tony_amd.models.inception_v3 import inception_v3
         model = inception_v3(fused=fused, seed=0, precision="fp32" if x3 else "bf16")
@@ -395,6 +413,12 @@ def main(argv=None):
                           branch_streams=not args.no_branch_streams, overlap_comm=not args.no_overlap)
     else:
         trainer = _PSOnly(ps, dev)
+    # --dump-outputs: the last timed step starts from the seeded initial training state, put back on the
+    # GPU right before it with the clock stopped.  The steps before it train on from wherever the setup
+    # and warmup steps (whose number and issue mode vary) left off, and the kernels' float atomics make
+    # every step differ from run to run in its rounding, which training amplifies step after step; one
+    # step from identical state differs by that rounding alone
+    initial = _training_state(ps, model, dev) if args.dump_outputs else None
     t_w = time.perf_counter()
     setup = {}
     if mode == "auto":
@@ -477,19 +501,28 @@ def main(argv=None):
     torch.cuda.synchronize()
     t0 = time.perf_counter()
     host = 0.0  # host time spent issuing the steps (the GPU must stay the bottleneck in eager mode)
-    for _ in range(args.steps):
+    paused = 0.0  # --dump-outputs: the clock stops while the state is put back before the last timed step
+    for i in range(args.steps):
+        if initial is not None and i == args.steps - 1:
+            torch.cuda.synchronize()
+            tp = time.perf_counter()
+            _restore_training_state(initial, ps, model, dev, trainer)
+            torch.cuda.synchronize()
+            paused = time.perf_counter() - tp
         th = time.perf_counter()
         loss = trainer.step(x, y)
         host += time.perf_counter() - th
     torch.cuda.synchronize()
     if world > 1:
         dist.barrier()
-    elapsed = time.perf_counter() - t0
-    # untimed: GPU time per step with the host far ahead (a spin kernel holds the GPU while the host
-    # enqueues the steps): equal to ms_per_step when the step is GPU-bound, lower when host launch
+    elapsed = time.perf_counter() - t0 - paused
+    if args.dump_outputs and rank == 0:  # before any untimed step below trains the variables further
+        _dump_outputs(args.dump_outputs, loss if ps.is_worker else None, model)
+    # untimed (--full): GPU time per step with the host far ahead (a spin kernel holds the GPU while the
+    # host enqueues the steps): equal to ms_per_step when the step is GPU-bound, lower when host launch
     # overhead leaves the GPU waiting
     gpu_ahead = host_free = None
-    if world == 1 and (trainer.use_graph is False or getattr(trainer, "plan", None) is not None):
+    if args.full and world == 1 and (trainer.use_graph is False or getattr(trainer, "plan", None) is not None):
         n_ahead = 6
         torch.cuda.synchronize()
         e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
@@ -502,15 +535,16 @@ def main(argv=None):
         e1.record()
         e1.synchronize()
         gpu_ahead = round(e0.elapsed_time(e1) / n_ahead, 3)
-    # untimed: one eager step with GPU events at the phase boundaries (fwd / bwd / exposed PS tail)
+    # untimed (--full): one eager step with GPU events at the phase boundaries (fwd / bwd / exposed PS tail)
     phases = None
-    was_graph = trainer.use_graph
-    trainer.use_graph = False
-    trainer.enable_phase_timing()
-    trainer.step(x, y)
-    phases = [max_over_ranks(v, device=dev) for v in trainer.phase_ms()]
-    trainer.phase_events = None
-    trainer.use_graph = was_graph
+    if args.full:
+        was_graph = trainer.use_graph
+        trainer.use_graph = False
+        trainer.enable_phase_timing()
+        trainer.step(x, y)
+        phases = [max_over_ranks(v, device=dev) for v in trainer.phase_ms()]
+        trainer.phase_events = None
+        trainer.use_graph = was_graph
     for _ in range(args.profile_steps):
         trainer.step(x, y)
     torch.cuda.synchronize()
@@ -547,7 +581,7 @@ def main(argv=None):
     eng_rank = ps.worker_ranks[0] if ps.worker_ranks else 0
     eng = dict(engines[eng_rank], engine_of_rank=eng_rank)
     fp32_row = None
-    if args.fp32_row and args.dtype == "bf16" and args.model == "inception_v3" and not args.stock:
+    if args.full and args.fp32_row and args.dtype == "bf16" and args.model == "inception_v3" and not args.stock:
         if world == 1:
             # reference precision under the same clock discipline: the x3 fp32 step in a child process
             fp32_row = _fp32_row(args)
@@ -576,6 +610,7 @@ def main(argv=None):
             "scaling": "weak",
             "vs_baseline": None,
             "dtype": args.dtype,
+            "full": args.full,
             "data": f"synthetic ImageNet-shaped {res}x{res}x3 batches, random-init weights",
             "config": {
                 "model": args.model,
@@ -595,7 +630,7 @@ def main(argv=None):
                 "wgrad_stream": not args.no_wgrad_stream,
                 "branch_streams": _branch_streams_on(args),
                 "grad_buckets": len(ps.buckets),
-                "phase_ms_eager_step_max_over_ranks":
+                "phase_ms_eager_step_max_over_ranks": None if phases is None else
                     dict(zip(("forward", "backward", "exposed_ps_push_apply_pull"), [round(v, 3) for v in phases])),
                 "kernels": "tony_amd HIP" if fused else (
                     "tony_amd HIP, fp32 via x3-split bf16 MFMA products (ops/x3.py)" if x3
@@ -637,6 +672,82 @@ def main(argv=None):
 # beat the plan by more than PLAN_TIE (TONY_PLAN_TIE / TONY_EAGER_HOST_BOUND)
 PLAN_TIE = float(os.environ.get("TONY_PLAN_TIE", "1.01"))
 EAGER_HOST_BOUND = float(os.environ.get("TONY_EAGER_HOST_BOUND", "0.8"))
+
+
+def _training_state(ps, model, dev) -> dict:
+    """A copy of everything a step reads and updates: the PS state (variables, fp32 masters, optimizer
+    state, step counts), the model's buffers (BN running statistics, dropout step counters) and the
+    generators' states; ``live`` / ``saved`` pair every live tensor with its copy, per dtype, so that
+    putting the state back is a few multi-tensor copies."""
+    sd = ps.state_dict()
+    live, saved = [ps.flat.data], [sd["flat"]]
+    for r, opt in ps.optimizers.items():
+        shard = sd["shards"][r]
+        live.append(opt.w)
+        saved.append(shard["master"])
+        cur = shard["opt"]  # the optimizer's state_dict hands out its live tensors
+        shard["opt"] = {k: v.detach().clone() if torch.is_tensor(v) else v for k, v in cur.items()}
+        for k, v in cur.items():
+            if torch.is_tensor(v):
+                live.append(v)
+                saved.append(shard["opt"][k])
+    buffers = {k: b.detach().clone() for k, b in model.named_buffers()}
+    for k, b in model.named_buffers():
+        live.append(b)
+        saved.append(buffers[k])
+    groups = {}
+    for a, b in zip(live, saved):
+        g = groups.setdefault((a.dtype, a.device), ([], []))
+        g[0].append(a)
+        g[1].append(b)
+    return {"ps": sd, "buffers": buffers, "groups": list(groups.values()),
+            "rng_cpu": torch.get_rng_state(), "rng_cuda": torch.cuda.get_rng_state(dev)}
+
+
+def _restore_training_state(state: dict, ps, model, dev, trainer) -> None:  # noqa: ARG001
+    """Put a ``_training_state`` copy back in place (every tensor keeps its address: a captured step
+    stays valid) and re-derive the trainer's per-step weight copies from the restored variables.
+    Enqueued on the current stream like a step (device copies of the state and one weight-cache
+    launch); the caller synchronizes."""
+    sd = state["ps"]
+    ps.steps = int(sd["steps"])
+    for r, opt in ps.optimizers.items():
+        o = sd["shards"][r]["opt"]
+        opt.step_count = int(o["step"])
+        opt.lr = float(o.get("lr", opt.lr))
+    with torch.no_grad():
+        for live, saved in state["groups"]:
+            torch._foreach_copy_(live, saved)
+    torch.set_rng_state(state["rng_cpu"])
+    torch.cuda.set_rng_state(state["rng_cuda"], dev)
+    for cache in (getattr(trainer, "wt", None), getattr(trainer, "wx3", None)):
+        if cache is not None:
+            cache.refresh()
+
+
+def _dump_outputs(directory: str, loss, model) -> None:
+    """What a caller of the timed step holds after the last timed step and can compare from run to run,
+    as float32 ``.npy`` files: ``loss`` (the step's return value) and ``bn_running_mean`` /
+    ``bn_running_var`` (the batch-norm running statistics that the step's forward updated, every
+    layer's in module order: one value per channel of every conv + BN layer).  A dedicated ps rank runs
+    no model and writes nothing.
+
+    The updated variables are not written.  One step from identical state moves them differently in
+    every run: the kernels sum in fp32 with float atomics, the order of the sums flips bf16 roundings,
+    and the backward pass through the randomly initialised conv + BN stack amplifies those flips until the
+    gradients of two runs differ by as much as the gradient itself in the first layers (relative L2
+    difference of the flat gradient ~1.0, variables up to 5e-2 apart after one step; loss and BN
+    statistics agree to a few 1e-4 and 1e-3 of their scale)."""
+    import numpy as np
+
+    if loss is None:
+        return
+    os.makedirs(directory, exist_ok=True)
+    np.save(os.path.join(directory, "loss.npy"), loss.detach().float().cpu().numpy().reshape(()))
+    for stat in ("running_mean", "running_var"):
+        bufs = [b.detach().float().reshape(-1) for k, b in model.named_buffers() if k.endswith("." + stat)]
+        if bufs:
+            np.save(os.path.join(directory, f"bn_{stat}.npy"), torch.cat(bufs).cpu().numpy().astype(np.float32))
 
 
 def _fp32_row(args) -> dict:

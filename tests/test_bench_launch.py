@@ -129,6 +129,46 @@ def test_rank_cpu_affinity_choice():
     assert rank_cpus(0, [0], devs, cpus_of_node=node.get, allowed=[100]) == []
 
 
+def test_plain_run_is_the_default_and_full_is_an_option():
+    """A plain run measures the headline only; the host-ahead window, the phase step and the fp32 row
+    run behind --full."""
+    sys.path.insert(0, ROOT)
+    import bench
+
+    a = bench.parse(["--gpus", "1", "--steps", "5", "--warmup", "2"])
+    assert a.full is False and a.dump_outputs is None and a.steps == 5 and a.warmup == 2
+    a = bench.parse(["--full", "--dump-outputs", "out"])
+    assert a.full is True and a.dump_outputs == "out"
+
+
+def test_dump_outputs_writes_float32_npy(tmp_path):
+    """--dump-outputs: the loss and every BN layer's running statistics, in module order, as float32
+    .npy; a rank without a model (no loss) writes nothing."""
+    import numpy as np
+    import torch
+    from torch import nn
+
+    sys.path.insert(0, ROOT)
+    import bench
+
+    m = nn.Sequential(nn.Conv2d(3, 4, 1), nn.BatchNorm2d(4), nn.Conv2d(4, 2, 1), nn.BatchNorm2d(2))
+    with torch.no_grad():
+        m[1].running_mean.copy_(torch.arange(4.0))
+        m[3].running_mean.copy_(torch.arange(4.0, 6.0))
+        m[1].running_var.fill_(0.5)
+        m[3].running_var.fill_(2.0)
+    bench._dump_outputs(str(tmp_path / "a"), torch.tensor(2.5, dtype=torch.bfloat16), m)
+    assert sorted(os.listdir(tmp_path / "a")) == ["bn_running_mean.npy", "bn_running_var.npy", "loss.npy"]
+    loss = np.load(tmp_path / "a" / "loss.npy")
+    assert loss.dtype == np.float32 and loss.shape == () and loss == 2.5
+    mean, var = np.load(tmp_path / "a" / "bn_running_mean.npy"), np.load(tmp_path / "a" / "bn_running_var.npy")
+    assert mean.dtype == var.dtype == np.float32
+    assert np.array_equal(mean, np.arange(6, dtype=np.float32))
+    assert np.array_equal(var, np.array([0.5] * 4 + [2.0] * 2, dtype=np.float32))
+    bench._dump_outputs(str(tmp_path / "b"), None, m)  # a dedicated ps rank
+    assert not (tmp_path / "b").exists()
+
+
 def test_ps_async_needs_dedicated_mode():
     """--ps-async is the paper topology's asynchronous PS (dedicated ps rank): refused with colocated shards,
     before any GPU call; passed through to the ranks of a self-launch."""

@@ -17,6 +17,8 @@ from tony_amd.conf import keys as K
 from tony_amd.utils import core as U
 
 FIX = os.path.join(os.path.dirname(os.path.abspath(__file__)), "fixtures")
+# files written by TonY itself (its example history, its parser test resources), stored with the tests
+GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
 
 
 # -- configuration ----------------------------------------------------------------------
@@ -463,10 +465,8 @@ def test_reads_tony_written_jhist_fixture():
     """A .jhist written by TonY's Java Avro writer (tony-portal example history) parses."""
     from tony_amd.events.avro import read_all
 
-    p = ("/root/reference/tony-portal/example/tony-history/finished/2019/01/08/application_123456_0001/"
-         "application_123456_0001-1546910478024-1546910517303-testuser-SUCCEEDED.jhist")
-    if not os.path.exists(p):
-        pytest.skip("reference tree not mounted")
+    p = os.path.join(GOLDEN, "tony-history", "finished", "2019", "01", "08", "application_123456_0001",
+                     "application_123456_0001-1546910478024-1546910517303-testuser-SUCCEEDED.jhist")
     ev = read_all(p)
     assert ev[0]["type"] == "APPLICATION_INITED" and ev[-1]["type"] == "APPLICATION_FINISHED"
 
@@ -511,10 +511,9 @@ def test_tony_final_xml_fixture_with_missing_subelements():
     """TTR/application_123_456/tony-final.xml has properties missing name/value."""
     from tony_amd.events.history import parse_config
 
-    d = "/root/reference/tony-core/src/test/resources/application_123_456"
-    if not os.path.exists(d):
-        pytest.skip("reference tree not mounted")
+    d = os.path.join(GOLDEN, "application_123_456")
     cfgs = parse_config(d)
+    assert {c.name for c in cfgs} >= {"fookey", "barkey", "bazkey"}
     assert all(c.name and c.value is not None for c in cfgs)
 
 

@@ -19,7 +19,8 @@ from tony_amd.portal import (CacheWrapper, HistoryFileMover, HistoryFilePurger, 
                              purge_intermediate_dir)
 from tony_amd.portal.history import killed_file_name, owner_alive, write_owner
 
-REF_HIST = "/root/reference/tony-portal/example/tony-history"
+# a history tree written by TonY itself (its portal's example: one finished job), stored with the tests
+REF_HIST = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "tony-history")
 
 
 def _job(inter, app_id, started, completed=None, status=None, user="alice"):
@@ -90,8 +91,7 @@ def test_purger_finished_and_intermediate(tmp_path):
 def portal(tmp_path):
     inter, fin = str(tmp_path / "intermediate"), str(tmp_path / "finished")
     os.makedirs(inter)
-    if os.path.isdir(REF_HIST):
-        shutil.copytree(os.path.join(REF_HIST, "finished"), fin)
+    shutil.copytree(os.path.join(REF_HIST, "finished"), fin)
     d = _job(inter, "application_7_0001", 1000, 5000, "FAILED", user="bob")
     write_owner(d, str(tmp_path / "staging" / "application_7_0001"))
     (tmp_path / "x.xml").write_text("")
@@ -112,12 +112,12 @@ def test_portal_pages(portal):
     jobs = _get(base + "/?format=json")
     ids = [j["id"] for j in jobs]
     assert "application_7_0001" in ids
-    if os.path.isdir(REF_HIST):  # the TonY-written example history renders too
-        assert ids[0] == "application_123456_0001"   # completed desc
-        ev = _get(base + "/jobs/application_123456_0001?format=json")
-        assert ev[0]["type"] == "APPLICATION_INITED"
-        assert any(c["name"] == "tony.worker.instances" for c in _get(base + "/config/application_123456_0001"
-                                                                        "?format=json"))
+    # the TonY-written example history renders too
+    assert ids[0] == "application_123456_0001"   # completed desc
+    ev = _get(base + "/jobs/application_123456_0001?format=json")
+    assert ev[0]["type"] == "APPLICATION_INITED"
+    assert any(c["name"] == "tony.worker.instances" for c in _get(base + "/config/application_123456_0001"
+                                                                    "?format=json"))
     cfg = _get(base + "/config/application_7_0001?format=json")
     assert any(c["name"] == "tony.application.framework" for c in cfg)
     logs = _get(base + "/logs/application_7_0001?format=json")

@@ -90,6 +90,49 @@ def test_graph_replay_matches_eager(cuda):
         assert err < 2e-2, (mode, err)
 
 
+@pytest.mark.parametrize("mode", ["eager", "graph_in"])
+def test_bench_restores_the_initial_training_state(cuda, mode):
+    """bench.py --dump-outputs puts the training state back before the timed steps: variables, masters,
+    momentum, step counts and buffers are the initial ones again, bit for bit, and the steps that follow
+    (eager or replayed from the capture made before the restore) train like the first ones did."""
+    import os
+    import sys
+
+    sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+    import bench
+    from tony_amd.models.layers import init_weights
+    from tony_amd.ops import cross_entropy
+    from tony_amd.parallel.ps import ParameterServer
+    from tony_amd.parallel.trainer import Trainer
+
+    dev = torch.device("cuda", 0)
+    model = init_weights(_Tiny(), seed=0).to(dev).to(memory_format=torch.channels_last).train()
+    ps = ParameterServer(model, optimizer="sgd", lr=0.05, momentum=0.9, device=dev)
+    tr = Trainer(model, ps, lambda o, y: cross_entropy(o, y), use_graph=mode != "eager", warmup_eager=1,
+                 graph_collectives=True if mode != "eager" else None)
+    g = torch.Generator(device=dev).manual_seed(7)
+    x = torch.randn((32, 16, 24, 24), generator=g, device=dev).to(torch.bfloat16)
+    x = x.contiguous(memory_format=torch.channels_last)
+    y = torch.randint(0, 10, (32,), generator=g, device=dev)
+    init = bench._training_state(ps, model, dev)
+    first = [float(tr.step(x, y).float().item()) for _ in range(3)]
+    p_first = ps.flat.data.float().clone()
+    assert not torch.equal(ps.flat.data, init["ps"]["flat"])
+    bench._restore_training_state(init, ps, model, dev, tr)
+    assert torch.equal(ps.flat.data, init["ps"]["flat"]) and ps.steps == 0
+    for r, opt in ps.optimizers.items():
+        assert torch.equal(opt.w, init["ps"]["shards"][r]["master"]) and opt.step_count == 0
+        assert not opt.v.any().item()  # momentum back at zero
+    for k, b in model.named_buffers():
+        assert torch.equal(b, init["buffers"][k]), k
+    again = [float(tr.step(x, y).float().item()) for _ in range(3)]
+    torch.cuda.synchronize()
+    assert ps.steps == 3
+    for a, b in zip(again, first):  # the bounds of test_graph_replay_matches_eager
+        assert abs(a - b) <= 2e-2 * max(1.0, abs(b)), (again, first)
+    assert (ps.flat.data.float() - p_first).abs().max().item() < 2e-2
+
+
 def test_transpose_batch_matches_permute(cuda):
     from tony_amd.ops.wt_cache import TransposedWeights
 

@@ -177,6 +177,14 @@ def main(argv=None) -> int:
     for s in range(start, total):
         if s == a.fail_at_step and os.environ.get("SESSION_ID", "0") == "0" and tc.task_type == "worker" \
                 and tc.task_index == 1:
+            # the hook kills the gang between two checkpoints, not during one: the shards of the last
+            # checkpoint step are written by background threads on every rank, and a gang torn down with
+            # one of them still in flight would resume from wherever the disk happened to be
+            due = (s // a.save_steps) * a.save_steps if a.save_steps else 0
+            ckpt.wait()
+            deadline = time.time() + 120
+            while due and (ckpt.latest() or (0, None))[0] < due and time.time() < deadline:
+                time.sleep(0.05)
             log(f"test hook: worker 1 fails at step {s}")
             os._exit(17)
         if s == timed_from:

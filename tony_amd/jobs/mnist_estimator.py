@@ -98,6 +98,9 @@ def main(argv=None) -> int:
         open(os.path.join(model_dir, "DONE"), "w").close()
         log(f"chief finished {a.steps} steps; checkpoints {[s for s, _ in ckpt.checkpoints()]}")
     dist.barrier()
+    # tear the process group down before interpreter exit: a rank that exits with the gloo threads still
+    # running can abort in their destructors ("terminate called without an active exception", exit 134)
+    dist.destroy_process_group()
     return 0
 
 

@@ -56,6 +56,7 @@ def main(argv=None) -> int:
             for _ in range(a.steps):
                 ps.step()
         dist.barrier()
+        dist.destroy_process_group()  # before interpreter exit (see the workers' shutdown below)
         return 0
     if tc.is_chief and os.environ.get("TB_PORT"):
         log(f"chief owns TensorBoard port {os.environ['TB_PORT']}")
@@ -76,6 +77,9 @@ def main(argv=None) -> int:
     metric(first_loss=losses[0], last_loss=losses[-1], worker=widx)
     log(f"worker {widx}: loss {losses[0]:.4f} -> {losses[-1]:.4f}")
     dist.barrier()
+    # tear the process group down before interpreter exit: a rank that exits with the gloo threads still
+    # running can abort in their destructors ("terminate called without an active exception", exit 134)
+    dist.destroy_process_group()
     return 0
 
 

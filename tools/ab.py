@@ -43,7 +43,7 @@ def main():
     for rep in range(a.reps):
         for name, env in arms:
             cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--steps", str(a.steps), "--warmup", "6",
-                   "--mode", a.mode] + a.bench_args.split()
+                   "--mode", a.mode, "--full"] + a.bench_args.split()  # --full: the gpu_ahead column below
             t = time.time()
             p = subprocess.run(cmd, env={**os.environ, **env}, capture_output=True, text=True, timeout=a.timeout)
             line = [ln for ln in p.stdout.splitlines() if ln.startswith("{")]

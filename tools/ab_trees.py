@@ -38,8 +38,11 @@ def main():
     os.makedirs(os.path.join(ROOT, "gpurun_out"), exist_ok=True)
     for rep in range(a.reps):
         for name, tree, env in arms:
-            cmd = [sys.executable, os.path.join(tree, "bench.py"), "--steps", str(a.steps), "--warmup",
-                   str(a.warmup), "--fp32-row", "0"] + a.bench_args.split()
+            bench = os.path.join(tree, "bench.py")
+            with open(bench) as f:  # --full (the gpu_ahead column below) where the tree's bench.py has it
+                full = ["--full"] if '"--full"' in f.read() else []
+            cmd = [sys.executable, bench, "--steps", str(a.steps), "--warmup", str(a.warmup), "--fp32-row", "0",
+                   *full] + a.bench_args.split()
             t = time.time()
             p = subprocess.run(cmd, cwd=tree, env={**os.environ, **env}, capture_output=True, text=True,
                                timeout=a.timeout)
