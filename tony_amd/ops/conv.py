@@ -269,17 +269,15 @@ def conv_dgrad(dy: torch.Tensor, weight: torch.Tensor, x_shape, stride=1, paddin
     vf = vflags if vflags is not None else tune.pick(("conv_dgrad", tuple(dy.shape), lddy, tuple(weight.shape),
                                                          (sh, sw), (ph, pw)), launch, tune.CONV_VARIANTS)
     if accum is not None and bnr is None and _accum_ok(accum, x_shape):
-        plain = dx
         dx = accum
         rc = launch(vf | 16)
-        if rc == 0:
-            return dx
-        if rc != -3:  # -3: the chosen tile variant has its own epilogue (halo / direct): add after
-            _lib.check(rc, name)
-        dx = plain
-        _lib.check(launch(vf), name)
-        accum.add_(dx)
-        return accum
+        if rc == -3 and (vf >> 8) & 0xff in (9, 10, tune.BAND_CODE):
+            # the halo / direct / band kernels have epilogues of their own without the accumulating store:
+            # the built-in NT tile adds instead, so the sum is rounded once whatever variant was picked (a
+            # bf16 dX added by a separate kernel would round twice)
+            rc = launch((vf & ~0xfff00) | 16)
+        _lib.check(rc, name)
+        return dx
     _lib.check(launch(vf, bnr), name)
     if accum is not None:
         accum.add_(dx)

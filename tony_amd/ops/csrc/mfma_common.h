@@ -292,12 +292,16 @@ __device__ __forceinline__ void nt_epilogue(f32x4 (&acc)[TM][TN], uint16_t* smem
                                             const RowMap rm = RowMap{}, bool f32out = false, bool accum = false,
                                             const uint16_t* __restrict__ asrc = nullptr,
                                             const uint8_t* __restrict__ amask = nullptr) {
-  // accum: C += the tile (bf16: the stored bf16 tile and C's old value summed in fp32 and rounded once,
-  // as the separate add kernel it replaces did) -- a backward-data GEMM adding its dX into the gradient
-  // another consumer of the same input already wrote (ResNet's identity path, ops/residual.py)
+  // accum: C += the tile -- a backward-data GEMM adding its dX into the gradient another consumer of the
+  // same input already wrote (ResNet's identity path, ops/residual.py).  bf16: C = bf16(acc + C's old
+  // value), the fp32 accumulators and the old value summed in fp32 and rounded ONCE (the tile is staged
+  // through LDS in fp32, half its rows at a time; rounding the tile to bf16 first, as the separate add
+  // kernel did, rounds twice and lands one ulp off where the first rounding makes a tie)
   // asrc / amask (bf16 C-shaped, row stride ldc, and its ReLU byte mask, row stride ldc / 8): C = the
   // tile + asrc masked by amask -- the other consumer's gradient dY * (y > 0) of a residual tail read
-  // where it lies instead of materialised first (ops/residual.py MaskedGrad); C's old value is unused
+  // where it lies instead of materialised first (ops/residual.py MaskedGrad); C's old value is unused.
+  // This masked form still sums the bf16-rounded tile and asrc (two roundings): only the plain accum
+  // above takes the fp32 staging
   constexpr int WM = BM / NWM, WN = BN / 2, NT = 128 * NWM;
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int wm = wave >> 1, wn = wave & 1;
@@ -351,6 +355,47 @@ __device__ __forceinline__ void nt_epilogue(f32x4 (&acc)[TM][TN], uint16_t* smem
   }
   constexpr int LDC = BN + 8;
   static_assert(BM * LDC <= LDS_ELEMS, "C staging tile must fit in the LDS buffers");
+  if (accum && asrc == nullptr) {
+    // fp32 staging (rows padded by 16 B), rows [p * BM / 2, (p + 1) * BM / 2) of the tile in pass p: the
+    // same 16-byte coalesced read-modify-write of C as the bf16 tile's, summed before the one rounding
+    constexpr int LDF = BN + 4, HALF = BM / 2;
+    static_assert(HALF * LDF * 2 <= LDS_ELEMS, "half an fp32 C tile must fit in the LDS buffers");
+    float* Cf = reinterpret_cast<float*>(smem);  // the K loop ended with a barrier: the buffers are free
+#pragma unroll
+    for (int p = 0; p < 2; ++p) {
+      if (p) __syncthreads();  // pass 0's reads of the staging area are done
+#pragma unroll
+      for (int i = 0; i < TM; ++i)
+#pragma unroll
+        for (int j = 0; j < TN; ++j)
+#pragma unroll
+          for (int r = 0; r < 4; ++r) {
+            const int row = wm * WM + i * 16 + (lane >> 4) * 4 + r;
+            const int col = wn * WN + j * 16 + (lane & 15);
+            if ((row >= HALF) == (p != 0)) Cf[(row - p * HALF) * LDF + col] = acc[i][j][r];
+          }
+      __syncthreads();
+      constexpr int HCHUNKS = HALF * BN / 8;
+      for (int v = threadIdx.x; v < HCHUNKS; v += NT) {
+        const int row = v / (BN / 8), ch = v % (BN / 8);
+        const int grow = m0 + p * HALF + row, gcol = n0 + ch * 8;
+        if (grow >= M || gcol >= N) continue;
+        const float* src = Cf + row * LDF + ch * 8;
+        uint16_t* dst = C + rm.pixel(grow) * ldc + gcol;
+        if (gcol + 8 <= N && (reinterpret_cast<uintptr_t>(dst) & 15) == 0) {
+          const float4 lo = *reinterpret_cast<const float4*>(src), hi = *reinterpret_cast<const float4*>(src + 4);
+          float a[8] = {lo.x, lo.y, lo.z, lo.w, hi.x, hi.y, hi.z, hi.w}, b[8];
+          load8(dst).to_float(b);
+#pragma unroll
+          for (int e = 0; e < 8; ++e) a[e] += b[e];
+          store8(dst, bf16x8::from_float(a));
+        } else {
+          for (int e = 0; e < 8 && gcol + e < N; ++e) dst[e] = f2bf(src[e] + bf2f(dst[e]));
+        }
+      }
+    }
+    return;
+  }
   uint16_t* Cs = smem;  // the K loop ended with a barrier: both buffers are free
   if (aff != nullptr) {
 #pragma unroll
@@ -388,32 +433,26 @@ __device__ __forceinline__ void nt_epilogue(f32x4 (&acc)[TM][TN], uint16_t* smem
     const uint16_t* src = Cs + row * LDC + ch * 8;
     uint16_t* dst = C + rm.pixel(grow) * ldc + gcol;
     if (gcol + 8 <= N && (reinterpret_cast<uintptr_t>(dst) & 15) == 0) {
-      if (accum) {
+      if (accum) {  // (the masked source: the plain accumulate returned above)
         float a[8], b[8];
         load8(src).to_float(a);
-        if (asrc != nullptr) {
-          const int64_t pix = rm.pixel(grow);
-          load8(asrc + pix * ldc + gcol).to_float(b);
-          const unsigned bits = amask[pix * (ldc >> 3) + (gcol >> 3)];
+        const int64_t pix = rm.pixel(grow);
+        load8(asrc + pix * ldc + gcol).to_float(b);
+        const unsigned bits = amask[pix * (ldc >> 3) + (gcol >> 3)];
 #pragma unroll
-          for (int e = 0; e < 8; ++e) a[e] += ((bits >> e) & 1u) ? b[e] : 0.f;
-        } else {
-          load8(dst).to_float(b);
-#pragma unroll
-          for (int e = 0; e < 8; ++e) a[e] += b[e];
-        }
+        for (int e = 0; e < 8; ++e) a[e] += ((bits >> e) & 1u) ? b[e] : 0.f;
         store8(dst, bf16x8::from_float(a));
       } else {
         *reinterpret_cast<uint4*>(dst) = *reinterpret_cast<const uint4*>(src);
       }
-    } else if (accum && asrc != nullptr) {
+    } else if (accum) {
       const int64_t pix = rm.pixel(grow);
       const unsigned bits = amask[pix * (ldc >> 3) + (gcol >> 3)];
       const uint16_t* as = asrc + pix * ldc + gcol;
       for (int e = 0; e < 8 && gcol + e < N; ++e)
         dst[e] = f2bf(bf2f(src[e]) + (((bits >> e) & 1u) ? bf2f(as[e]) : 0.f));
     } else {
-      for (int e = 0; e < 8 && gcol + e < N; ++e) dst[e] = accum ? f2bf(bf2f(src[e]) + bf2f(dst[e])) : src[e];
+      for (int e = 0; e < 8 && gcol + e < N; ++e) dst[e] = src[e];
     }
   }
 }
