@@ -18,6 +18,12 @@ import pytest
 import torch
 import torch.nn.functional as F
 
+from exact_helpers import SENT as _SENT
+from exact_helpers import Slab as _Slab
+from exact_helpers import assert_equal as _assert_equal
+from exact_helpers import pix_rows as _pix_rows
+from exact_helpers import poisoned as _poisoned
+
 pytestmark = pytest.mark.gpu
 
 _BF16 = torch.bfloat16
@@ -111,18 +117,6 @@ def _gpu(shape, amp=2):
 def _krsc_flat(t):
     """[Co, Ci, R, S] -> flat [Co][R][S][Ci] (the memory order of a weight-gradient slot)."""
     return t.permute(0, 2, 3, 1).contiguous().reshape(-1)
-
-
-def _assert_equal(got, want, what):
-    """``torch.equal`` on the whole tensor; on failure the count and first coordinates of the differences."""
-    assert got.shape == want.shape, f"{what}: shape {tuple(got.shape)} != {tuple(want.shape)}"
-    assert got.dtype == want.dtype, f"{what}: dtype {got.dtype} != {want.dtype}"
-    if torch.equal(got, want):
-        return
-    bad = (got != want) | (got != got)
-    first = [tuple(i) for i in bad.nonzero()[:8].tolist()]
-    detail = ", ".join(f"{i}: got {got[i].item()} want {want[i].item()}" for i in first)
-    pytest.fail(f"{what}: {int(bad.sum())} of {got.numel()} elements differ; first {detail}")
 
 
 _DECLINED = object()
@@ -429,52 +423,6 @@ def test_x3_exact(cuda, shape, code, monkeypatch):
 
 
 # --------------------------------------------------- B: poisoned operands, guarded destinations --
-_SENT = 1.5  # the finite sentinel of every destination's surroundings (no integer: a result never equals it)
-
-
-def _guard_elems(ld, dtype):
-    """Elements of one guard: at least 2 x 256 rows of the operand's row stride, never less than 64 KB."""
-    esz = torch.empty((), dtype=dtype).element_size()
-    return -(-max(2 * 256 * ld, 65536 // esz) // 8) * 8
-
-
-class _Slab:
-    """``rows`` x ``cols`` elements at channel offset ``c0`` of rows ``ld = cols + 2 * c0`` wide, inside one
-    flat allocation filled with ``fill`` that extends a guard before the first and after the last row."""
-
-    def __init__(self, rows, cols, c0, dtype, fill, device, guard_ld=None):
-        self.rows, self.cols, self.c0, self.ld, self.fill = rows, cols, c0, cols + 2 * c0, fill
-        # (a flat destination -- dW, statistics -- has no row stride: the guard is sized by ``guard_ld``)
-        self.guard = _guard_elems(guard_ld or self.ld, dtype)
-        self.alloc = torch.full((2 * self.guard + rows * self.ld,), fill, dtype=dtype, device=device)
-        self.view = self._inner(self.alloc)
-        assert self.view.data_ptr() % 16 == 0 and self.ld % 8 == 0
-
-    def _inner(self, alloc):
-        body = alloc[self.guard:self.guard + self.rows * self.ld].view(self.rows, self.ld)
-        return body[:, self.c0:self.c0 + self.cols]
-
-    def ptr(self):
-        return self.view.data_ptr()
-
-    def assert_surroundings_intact(self, what):
-        rest = self.alloc.clone()
-        self._inner(rest).fill_(self.fill)
-        assert torch.equal(rest, torch.full_like(rest, self.fill)), f"{what}: bytes outside the destination changed"
-
-
-def _poisoned(rows2d, c0):
-    """The [rows, cols] operand as a channel slice of a NaN-filled allocation with NaN guards."""
-    s = _Slab(rows2d.shape[0], rows2d.shape[1], c0, rows2d.dtype, float("nan"), rows2d.device)
-    s.view.copy_(rows2d)
-    return s
-
-
-def _pix_rows(t):
-    """[N, C, H, W] -> [N*H*W, C] rows (NHWC order)."""
-    return t.permute(0, 2, 3, 1).reshape(-1, t.shape[1])
-
-
 def _stats_slab(co, device):
     from tony_amd.ops import _lib
 
