@@ -30,13 +30,16 @@ def main(argv=None) -> int:
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--batch-size", type=int, default=128)
     ap.add_argument("--lr", type=float, default=0.001)
+    ap.add_argument("--fused", action="store_true",
+                    help="apply Adam with the fused HIP kernel over the flat parameter buffer (GPU ranks)")
     a = ap.parse_args(argv)
     hvd.init()
     dev = hvd.device()
     log(f"hvd rank {hvd.rank()}/{hvd.size()} local {hvd.local_rank()}/{hvd.local_size()} on {dev}")
     model = mnist_model("hvd_cnn", seed=hvd.rank()).to(dev)
     opt = torch.optim.Adam(model.parameters(), lr=a.lr * hvd.size())
-    opt = hvd.DistributedOptimizer(opt, named_parameters=model.named_parameters())
+    opt = hvd.DistributedOptimizer(opt, named_parameters=model.named_parameters(),
+                                   fused=True if a.fused else None)
     hvd.broadcast_parameters(model.state_dict(), root_rank=0)
     hvd.broadcast_optimizer_state(opt, root_rank=0)
     x_all, y_all = synthetic_mnist(a.batch_size * hvd.size() * 4, seed=7, device=dev)

@@ -69,6 +69,9 @@ def main(argv=None) -> int:
                     help="compute precision on GPU: bf16 (default) or fp32 -- the reference job's precision "
                          "(mnist_distributed.py: fp32 variables and compute): fp32 activations, variables and "
                          "pushed gradients, each conv / GEMM product as an x3 split over the bf16 MFMA kernels")
+    ap.add_argument("--optimizer", default="sgd", choices=["sgd", "rmsprop_tf"],
+                    help="sgd (default): momentum SGD; rmsprop_tf: the model's published recipe (RMSProp in TF's "
+                         "form, decay 0.9, momentum 0.9, epsilon 1.0)")
     a = ap.parse_args(argv)
     tc = TFConfig.from_env()
     on_gpu = torch.cuda.is_available()
@@ -98,7 +101,7 @@ def main(argv=None) -> int:
         model = inception_v3(fused=False, seed=0, precision="fp32").to(dev).to(memory_format=torch.channels_last)
     else:
         model = cast_model(inception_v3(fused=on_gpu, seed=0), dtype, dev).to(memory_format=torch.channels_last)
-    ps = ParameterServer(model, optimizer="sgd", lr=0.045, momentum=0.9, weight_decay=4e-5, mode=mode,
+    ps = ParameterServer(model, optimizer=a.optimizer, lr=0.045, momentum=0.9, weight_decay=4e-5, mode=mode,
                          ps_ranks=tc.ps_ranks if mode == "dedicated" else (0,), dtype=dtype, device=dev,
                          wire_dtype=torch.float32 if dtype == torch.float32 else None,
                          sync=not (a.async_ps and mode == "dedicated"))

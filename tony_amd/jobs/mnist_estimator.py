@@ -9,7 +9,10 @@ DNNClassifier([256, 128]), ``RunConfig(save_checkpoints_steps, keep_checkpoint_m
   TonY drops it from everyone else's view): it polls the model dir, evaluates each new
   checkpoint on held-out synthetic data, and exits after evaluating the final one.
 
-Adagrad (the Estimator default) is replaced by the fused Adam of tony_amd.ops.optim.
+The default optimizer is the fused Adam of tony_amd.ops.optim; ``--optimizer adagrad`` trains with the
+reference job's own ``Adagrad(learning_rate, epsilon=1e-5)`` (the fused Adagrad, accumulator starting at 0.1):
+
+  tony --src_dir tony_amd/jobs --executes mnist_estimator.py --task_params '--optimizer adagrad' ...
 
   tony --src_dir tony_amd/jobs --executes mnist_estimator.py --conf tony.chief.instances=1 \
        --conf tony.worker.instances=2 --conf tony.ps.instances=1 --conf tony.evaluator.instances=1
@@ -70,6 +73,9 @@ def main(argv=None) -> int:
     ap.add_argument("--save-steps", type=int, default=5)
     ap.add_argument("--batch-size", type=int, default=64)
     ap.add_argument("--eval-timeout", type=float, default=600)
+    ap.add_argument("--optimizer", default="adam", choices=["adam", "adagrad"],
+                    help="adam (default) or adagrad, the reference job's optimizer (epsilon 1e-5)")
+    ap.add_argument("--lr", type=float, default=1e-3, help="learning rate (the reference job's default)")
     a = ap.parse_args(argv)
     tc = TFConfig.from_env()
     model_dir = working_dir("estimator_model")
@@ -77,8 +83,9 @@ def main(argv=None) -> int:
         return evaluate(a, model_dir)
     rank, world, dev = bootstrap.init_from_tf_config(tc)
     model = mnist_model("dnn", seed=0).to(dev)
-    ps = ParameterServer(model, optimizer="adam", lr=1e-3, mode="dedicated", sync=True, ps_ranks=tc.ps_ranks,
-                         dtype=torch.float32, device=dev)
+    opt_kw = {"eps": 1e-5} if a.optimizer == "adagrad" else {}
+    ps = ParameterServer(model, optimizer=a.optimizer, lr=a.lr, mode="dedicated", sync=True, ps_ranks=tc.ps_ranks,
+                         dtype=torch.float32, device=dev, **opt_kw)
     ckpt = CheckpointManager(model_dir, keep_max=3, save_steps=a.save_steps, rank=0 if tc.is_chief else 1)
     if tc.is_chief and os.path.exists(os.path.join(model_dir, "DONE")):
         os.remove(os.path.join(model_dir, "DONE"))
@@ -88,8 +95,10 @@ def main(argv=None) -> int:
         if ps.is_worker:
             lo = (((s - 1) % 4) * len(ps.worker_ranks) + widx) * a.batch_size
             ps.zero_grad()
-            torch.nn.functional.cross_entropy(model(x_all[lo:lo + a.batch_size]),
-                                              y_all[lo:lo + a.batch_size]).backward()
+            loss = torch.nn.functional.cross_entropy(model(x_all[lo:lo + a.batch_size]), y_all[lo:lo + a.batch_size])
+            loss.backward()
+            if tc.is_chief and (s == 1 or s % max(1, a.save_steps) == 0 or s == a.steps):
+                log(f"step {s}: loss {float(loss):.4f} ({a.optimizer})")
         ps.step()
         ckpt.save(s, {"flat": ps.flat.data})
     if tc.is_chief:

@@ -15,6 +15,9 @@
 //        broadcast_parameters from rank 0, a checkpoint restore into the module) and its master is
 //        re-seeded from it before the update -- one extra 2-byte read per parameter
 //   Adam hp = [lr, beta1, beta2, eps, weight_decay, grad_scale, bias_corr1, bias_corr2, decoupled]
+//   Adagrad hp = [lr, eps, weight_decay, grad_scale]
+//   RMSProp hp = [lr, alpha, momentum, eps, weight_decay, grad_scale, tf_style]
+//        tf_style != 0: TF's form (eps inside the root, lr folded into the momentum; optim_math.h)
 #include "common.h"
 #include "optim_math.h"
 
@@ -110,6 +113,55 @@ __global__ __launch_bounds__(kThreads) void adam_kernel(float* __restrict__ w, f
   }
 }
 
+template <bool kGradBf16>
+__global__ __launch_bounds__(kThreads) void adagrad_kernel(float* __restrict__ w, float* __restrict__ h,
+                                                           const void* __restrict__ g,
+                                                           uint16_t* __restrict__ w_bf16, int64_t n4,
+                                                           const float* __restrict__ hp) {
+  const float lr = hp[0], eps = hp[1], wd = hp[2], gs = hp[3];
+  const int64_t stride = static_cast<int64_t>(gridDim.x) * kThreads;
+  for (int64_t q = static_cast<int64_t>(blockIdx.x) * kThreads + threadIdx.x; q < n4; q += stride) {
+    const int64_t i = q * 4;
+    float gf[4];
+    load_grad4<kGradBf16>(g, i, gf);
+    float4 wv = *reinterpret_cast<float4*>(w + i);
+    float4 hv = *reinterpret_cast<float4*>(h + i);
+    float wf[4] = {wv.x, wv.y, wv.z, wv.w};
+    float hf[4] = {hv.x, hv.y, hv.z, hv.w};
+    adagrad_update4(wf, hf, gf, lr, eps, wd, gs);
+    *reinterpret_cast<float4*>(w + i) = make_float4(wf[0], wf[1], wf[2], wf[3]);
+    *reinterpret_cast<float4*>(h + i) = make_float4(hf[0], hf[1], hf[2], hf[3]);
+    if (w_bf16 != nullptr) store_bf16x4(w_bf16 + i, wf);
+  }
+}
+
+template <bool kGradBf16>
+__global__ __launch_bounds__(kThreads) void rmsprop_kernel(float* __restrict__ w, float* __restrict__ ms,
+                                                           float* __restrict__ mom,
+                                                           const void* __restrict__ g,
+                                                           uint16_t* __restrict__ w_bf16, int64_t n4,
+                                                           const float* __restrict__ hp) {
+  const float lr = hp[0], alpha = hp[1], mu = hp[2], eps = hp[3], wd = hp[4], gs = hp[5];
+  const bool tf_style = hp[6] != 0.f;
+  const int64_t stride = static_cast<int64_t>(gridDim.x) * kThreads;
+  for (int64_t q = static_cast<int64_t>(blockIdx.x) * kThreads + threadIdx.x; q < n4; q += stride) {
+    const int64_t i = q * 4;
+    float gf[4];
+    load_grad4<kGradBf16>(g, i, gf);
+    float4 wv = *reinterpret_cast<float4*>(w + i);
+    float4 sv = *reinterpret_cast<float4*>(ms + i);
+    float4 mv = *reinterpret_cast<float4*>(mom + i);
+    float wf[4] = {wv.x, wv.y, wv.z, wv.w};
+    float sf[4] = {sv.x, sv.y, sv.z, sv.w};
+    float mf[4] = {mv.x, mv.y, mv.z, mv.w};
+    rmsprop_update4(wf, sf, mf, gf, lr, alpha, mu, eps, wd, gs, tf_style);
+    *reinterpret_cast<float4*>(w + i) = make_float4(wf[0], wf[1], wf[2], wf[3]);
+    *reinterpret_cast<float4*>(ms + i) = make_float4(sf[0], sf[1], sf[2], sf[3]);
+    *reinterpret_cast<float4*>(mom + i) = make_float4(mf[0], mf[1], mf[2], mf[3]);
+    if (w_bf16 != nullptr) store_bf16x4(w_bf16 + i, wf);
+  }
+}
+
 // Sum of squares + non-finite flag over a flat bf16/fp32 gradient (H12):
 // out[0] += sum(g^2), out[1] = 1 if any element is inf/nan.
 template <bool kGradBf16>
@@ -169,6 +221,30 @@ TONY_API int tony_adam_step(float* w, float* m, float* v, const void* g, int gra
     adam_kernel<true><<<grid_for(n4), kThreads, 0, stream>>>(w, m, v, g, static_cast<uint16_t*>(w_bf16), n4, hp);
   else
     adam_kernel<false><<<grid_for(n4), kThreads, 0, stream>>>(w, m, v, g, static_cast<uint16_t*>(w_bf16), n4, hp);
+  TONY_LAUNCH_CHECK();
+  return 0;
+}
+
+TONY_API int tony_adagrad_step(float* w, float* h, const void* g, int grad_bf16, void* w_bf16, int64_t n,
+                               const float* hp, hipStream_t stream) {
+  if (n % 4) return -1;
+  const int64_t n4 = n / 4;
+  if (grad_bf16)
+    adagrad_kernel<true><<<grid_for(n4), kThreads, 0, stream>>>(w, h, g, static_cast<uint16_t*>(w_bf16), n4, hp);
+  else
+    adagrad_kernel<false><<<grid_for(n4), kThreads, 0, stream>>>(w, h, g, static_cast<uint16_t*>(w_bf16), n4, hp);
+  TONY_LAUNCH_CHECK();
+  return 0;
+}
+
+TONY_API int tony_rmsprop_step(float* w, float* ms, float* mom, const void* g, int grad_bf16, void* w_bf16,
+                               int64_t n, const float* hp, hipStream_t stream) {
+  if (n % 4) return -1;
+  const int64_t n4 = n / 4;
+  if (grad_bf16)
+    rmsprop_kernel<true><<<grid_for(n4), kThreads, 0, stream>>>(w, ms, mom, g, static_cast<uint16_t*>(w_bf16), n4, hp);
+  else
+    rmsprop_kernel<false><<<grid_for(n4), kThreads, 0, stream>>>(w, ms, mom, g, static_cast<uint16_t*>(w_bf16), n4, hp);
   TONY_LAUNCH_CHECK();
   return 0;
 }

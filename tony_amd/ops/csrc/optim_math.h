@@ -1,6 +1,7 @@
 // The element-wise optimizer updates shared by the flat-shard apply kernels (optim.hip) and the
 // parameter-server data plane (ps_plane.hip): 4 elements per call, fp32 math, TF / torch.optim
-// semantics (SGD with (Nesterov) momentum and L2 weight decay; Adam / AdamW with bias correction).
+// semantics (SGD with (Nesterov) momentum and L2 weight decay; Adam / AdamW with bias correction;
+// Adagrad; RMSProp in torch's and in TF's form).
 #pragma once
 #include "common.h"
 
@@ -34,6 +35,36 @@ __device__ __forceinline__ void adam_update4(float* wf, float* mf, float* vf, co
     vf[k] = fmaf(b2, vf[k], (1.f - b2) * gk * gk);
     const float denom = sqrtf(vf[k]) * inv_sqrt_bc2 + eps;
     wf[k] = fmaf(-step_size, mf[k] / denom, wf[k]);
+  }
+}
+
+// g' = g gs + wd w;  h += g'^2;  w -= lr g' / (sqrt(h) + eps)   (torch.optim.Adagrad, lr_decay 0; Keras Adagrad)
+__device__ __forceinline__ void adagrad_update4(float* wf, float* hf, const float* gf, float lr, float eps, float wd,
+                                                float gs) {
+#pragma unroll
+  for (int k = 0; k < 4; ++k) {
+    const float gk = fmaf(gf[k], gs, wd * wf[k]);
+    hf[k] = fmaf(gk, gk, hf[k]);
+    wf[k] = fmaf(-lr, gk / (sqrtf(hf[k]) + eps), wf[k]);
+  }
+}
+
+// g' = g gs + wd w;  ms = alpha ms + (1-alpha) g'^2   (not centered; mom is kept even when mu = 0)
+//   torch (tf_style false): mom = mu mom + g' / (sqrt(ms) + eps);      w -= lr mom   (torch.optim.RMSprop)
+//   TF    (tf_style true):  mom = mu mom + lr g' / sqrt(ms + eps);     w -= mom      (tf.train.RMSPropOptimizer)
+__device__ __forceinline__ void rmsprop_update4(float* wf, float* sf, float* mf, const float* gf, float lr,
+                                                float alpha, float mu, float eps, float wd, float gs, bool tf_style) {
+#pragma unroll
+  for (int k = 0; k < 4; ++k) {
+    const float gk = fmaf(gf[k], gs, wd * wf[k]);
+    sf[k] = fmaf(alpha, sf[k], (1.f - alpha) * gk * gk);
+    if (tf_style) {
+      mf[k] = fmaf(mu, mf[k], lr * gk / sqrtf(sf[k] + eps));
+      wf[k] -= mf[k];
+    } else {
+      mf[k] = fmaf(mu, mf[k], gk / (sqrtf(sf[k]) + eps));
+      wf[k] = fmaf(-lr, mf[k], wf[k]);
+    }
   }
 }
 

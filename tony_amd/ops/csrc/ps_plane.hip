@@ -17,8 +17,8 @@
 //          straight into row w of P's receive rows (remote stores over the w<->P link), then
 //          publishes arrival[b][w][c] in P's window (system-scope release).
 //   apply  (P): workgroup c waits for chunk c of every worker's row (sync) and runs the fused
-//          optimizer over it: sum of the rows (fp32) x grad_scale -> SGD / Adam on the fp32 master
-//          and state -> the new variables are stored straight into EVERY worker's landing zone
+//          optimizer over it: sum of the rows (fp32) x grad_scale -> SGD / Adam / Adagrad / RMSProp on the fp32
+//          master and state -> the new variables are stored straight into EVERY worker's landing zone
 //          (remote stores: P drives its 7 links at once) -> landed[b][c] in each worker's window.
 //          Async (TF's default PS): workgroup c applies each worker's row on its own as it
 //          arrives and lands the result only in THAT worker's zone (its pull sees its own push
@@ -144,8 +144,8 @@ struct ApplyArgs {
   int nworkers;
   int64_t n;                // elements of the bucket
   float* master;            // fp32 master of the bucket (ps-local)
-  float* s0;                // SGD momentum / Adam m
-  float* s1;                // Adam v (unused for SGD)
+  float* s0;                // SGD momentum / Adam m / Adagrad h / RMSProp ms
+  float* s1;                // Adam v / RMSProp mom (unused for SGD and Adagrad)
   const float* hp;          // csrc/optim.hip hyper-parameter layout
   void* out[kMaxRanks];     // each worker's landing zone at the bucket (remote)
   void* local_out;          // the ps's own flat parameters at the bucket (may be null)
@@ -165,11 +165,16 @@ __device__ __forceinline__ void update4(const ApplyArgs& a, int64_t i, const flo
   float mf[4] = {mv.x, mv.y, mv.z, mv.w};
   if constexpr (OPT == 0) {
     sgd_update4(wf, mf, g, hp[0], hp[1], hp[2], hp[3], hp[4] != 0.f);
+  } else if constexpr (OPT == 2) {
+    adagrad_update4(wf, mf, g, hp[0], hp[1], hp[2], hp[3]);
   } else {
     float4 vv = *reinterpret_cast<float4*>(a.s1 + i);
     float vf[4] = {vv.x, vv.y, vv.z, vv.w};
-    adam_update4(wf, mf, vf, g, hp[0], hp[1], hp[2], hp[3], hp[4], hp[5], hp[0] / hp[6], rsqrtf(hp[7]),
-                 hp[8] != 0.f);
+    if constexpr (OPT == 1)
+      adam_update4(wf, mf, vf, g, hp[0], hp[1], hp[2], hp[3], hp[4], hp[5], hp[0] / hp[6], rsqrtf(hp[7]),
+                   hp[8] != 0.f);
+    else
+      rmsprop_update4(wf, mf, vf, g, hp[0], hp[1], hp[2], hp[3], hp[4], hp[5], hp[6] != 0.f);
     *reinterpret_cast<float4*>(a.s1 + i) = make_float4(vf[0], vf[1], vf[2], vf[3]);
   }
   *reinterpret_cast<float4*>(a.master + i) = make_float4(wf[0], wf[1], wf[2], wf[3]);
@@ -471,7 +476,8 @@ TONY_API int tony_ps_apply(void* ps_window, int64_t rows_off, int64_t row_stride
                            const uint64_t* worker_windows, void* local_params, int param_bf16, int bucket,
                            uint32_t value, int async_mode, double budget_s, int blocks, hipStream_t stream) {
   if (ps_window == nullptr || nworkers < 1 || nworkers > kMaxRanks || n <= 0 || (n % 8) || lo < 0 || (lo % 8) ||
-      master == nullptr || s0 == nullptr || hp == nullptr || (opt == 1 && s1 == nullptr) || opt < 0 || opt > 1 ||
+      master == nullptr || s0 == nullptr || hp == nullptr || opt < 0 || opt > 3 ||
+      ((opt == 1 || opt == 3) && s1 == nullptr) ||  // Adam and RMSProp keep two states
       bucket < 0 || bucket >= kMaxBuckets || value == 0 || blocks < 1 || blocks > kMaxBlocks ||
       (row_stride % 16) || (rows_off % 16) || worker_windows == nullptr)
     return -1;
@@ -508,18 +514,17 @@ TONY_API int tony_ps_apply(void* ps_window, int64_t rows_off, int64_t row_stride
   };
   using T = std::true_type;
   using F = std::false_type;
-  using O0 = std::integral_constant<int, 0>;
-  using O1 = std::integral_constant<int, 1>;
-  if (opt == 0) {
+  const auto go_opt = [&](auto opt_c) {
     if (wire_bf16)
-      param_bf16 ? go(O0{}, T{}, T{}) : go(O0{}, T{}, F{});
+      param_bf16 ? go(opt_c, T{}, T{}) : go(opt_c, T{}, F{});
     else
-      param_bf16 ? go(O0{}, F{}, T{}) : go(O0{}, F{}, F{});
-  } else {
-    if (wire_bf16)
-      param_bf16 ? go(O1{}, T{}, T{}) : go(O1{}, T{}, F{});
-    else
-      param_bf16 ? go(O1{}, F{}, T{}) : go(O1{}, F{}, F{});
+      param_bf16 ? go(opt_c, F{}, T{}) : go(opt_c, F{}, F{});
+  };
+  switch (opt) {  // 0 SGD, 1 Adam, 2 Adagrad, 3 RMSProp
+    case 0: go_opt(std::integral_constant<int, 0>{}); break;
+    case 1: go_opt(std::integral_constant<int, 1>{}); break;
+    case 2: go_opt(std::integral_constant<int, 2>{}); break;
+    default: go_opt(std::integral_constant<int, 3>{}); break;
   }
   TONY_LAUNCH_CHECK();
   return 0;

@@ -1,7 +1,7 @@
 """Fused optimizers over flat parameter shards (HIP kernels in csrc/optim.hip).
 
-``FlatSGD`` / ``FlatAdam`` own an fp32 master copy of a flat parameter shard
-plus its optimizer state, consume a flat gradient (bf16 or fp32) and write the
+``FlatSGD`` / ``FlatAdam`` / ``FlatAdagrad`` / ``FlatRMSProp`` own an fp32 master copy of a flat parameter
+shard plus its optimizer state, consume a flat gradient (bf16 or fp32) and write the
 updated bf16 compute copy in the same pass.  The PS shard (``tony_amd.parallel.ps``)
 and the data-parallel engine use them directly; on CPU tensors the same update
 is computed with PyTorch ops (used by the CPU test-suite and local mode).
@@ -66,6 +66,11 @@ class _FlatOptimizer:
     def state_dict(self):
         raise NotImplementedError
 
+    def plane_state(self):
+        """``(opt, s0, s1)`` for the PS data plane's apply kernel (csrc/ps_plane.hip ``tony_ps_apply``): its
+        optimizer code and the one or two state tensors it updates beside the master (``s1`` may be None)."""
+        raise NotImplementedError
+
 
 class FlatSGD(_FlatOptimizer):
     """SGD with (Nesterov) momentum: v = mu*v + g + wd*w ; w -= lr*v (TF MomentumOptimizer semantics)."""
@@ -116,6 +121,9 @@ class FlatSGD(_FlatOptimizer):
         self.step_count = int(sd["step"])
         self.v.copy_(sd["momentum_buffer"])
         self.lr = float(sd.get("lr", self.lr))
+
+    def plane_state(self):
+        return 0, self.v, None
 
 
 class FlatAdam(_FlatOptimizer):
@@ -169,6 +177,117 @@ class FlatAdam(_FlatOptimizer):
         self.m.copy_(sd["exp_avg"])
         self.v.copy_(sd["exp_avg_sq"])
         self.lr = float(sd.get("lr", self.lr))
+
+    def plane_state(self):
+        return 1, self.m, self.v
+
+
+class FlatAdagrad(_FlatOptimizer):
+    """Adagrad: g' = g + wd*w ; h += g'^2 ; w -= lr*g' / (sqrt(h) + eps)  (``torch.optim.Adagrad`` with
+    ``lr_decay=0``, Keras ``Adagrad``); ``h`` starts at ``initial_accumulator_value``."""
+
+    n_hp = 4
+
+    def __init__(self, master, lr, eps=1e-7, initial_accumulator_value=0.1, weight_decay=0.0):
+        super().__init__(master, lr, weight_decay)
+        self.eps = float(eps)
+        self.h = torch.full_like(master, float(initial_accumulator_value))
+
+    def _hp_values(self):
+        return [self.lr, self.eps, self.weight_decay, self.grad_scale]
+
+    def apply_range(self, grad: torch.Tensor, lo: int = 0, out_bf16: torch.Tensor | None = None):
+        n = grad.numel()
+        if lo < 0 or lo + n > self.w.numel() or lo % 4 or n % 4:
+            raise ValueError(f"range [{lo}, {lo + n}) outside the {self.w.numel()}-element shard or not 4-aligned")
+        if self.w.is_cuda:
+            rc = _lib.lib().tony_adagrad_step(self.w.data_ptr() + 4 * lo, self.h.data_ptr() + 4 * lo,
+                                              grad.data_ptr(), int(grad.dtype == torch.bfloat16),
+                                              _lib.ptr(out_bf16), n, self._hp_dev.data_ptr(),
+                                              _lib.stream_ptr(self.w.device))
+            _lib.check(rc, "tony_adagrad_step")
+            return
+        w, h = self.w[lo:lo + n], self.h[lo:lo + n]
+        g = grad.float() * self.grad_scale + self.weight_decay * w
+        h.addcmul_(g, g)
+        w.addcdiv_(g, h.sqrt().add_(self.eps), value=-self.lr)
+        if out_bf16 is not None:
+            out_bf16.copy_(w)
+
+    def state_dict(self):
+        return {"kind": "adagrad", "step": self.step_count, "sum": self.h, "lr": self.lr}
+
+    def load_state_dict(self, sd):
+        self.step_count = int(sd["step"])
+        self.h.copy_(sd["sum"])
+        self.lr = float(sd.get("lr", self.lr))
+
+    def plane_state(self):
+        return 2, self.h, None
+
+
+class FlatRMSProp(_FlatOptimizer):
+    """RMSProp (not centered): g' = g + wd*w ; ms = alpha*ms + (1-alpha)*g'^2, then
+
+    torch style (``tf_style=False``, ``torch.optim.RMSprop``): mom = momentum*mom + g'/(sqrt(ms) + eps) ;
+    w -= lr*mom ; ``ms`` starts at 0;
+    TF style (``tf_style=True``, ``tf.train.RMSPropOptimizer``, the Inception recipe): mom = momentum*mom +
+    lr*g'/sqrt(ms + eps) ; w -= mom ; ``ms`` starts at 1.
+
+    Both states are always kept; ``momentum=0`` falls out of the same formula."""
+
+    n_hp = 7
+
+    def __init__(self, master, lr, alpha=0.9, momentum=0.0, eps=1e-8, weight_decay=0.0, tf_style=False):
+        super().__init__(master, lr, weight_decay)
+        self.alpha = float(alpha)
+        self.momentum = float(momentum)
+        self.eps = float(eps)
+        self.tf_style = bool(tf_style)
+        self.ms = torch.ones_like(master) if self.tf_style else torch.zeros_like(master)
+        self.mom = torch.zeros_like(master)
+
+    def _hp_values(self):
+        return [self.lr, self.alpha, self.momentum, self.eps, self.weight_decay, self.grad_scale,
+                1.0 if self.tf_style else 0.0]
+
+    def apply_range(self, grad: torch.Tensor, lo: int = 0, out_bf16: torch.Tensor | None = None):
+        n = grad.numel()
+        if lo < 0 or lo + n > self.w.numel() or lo % 4 or n % 4:
+            raise ValueError(f"range [{lo}, {lo + n}) outside the {self.w.numel()}-element shard or not 4-aligned")
+        if self.w.is_cuda:
+            rc = _lib.lib().tony_rmsprop_step(self.w.data_ptr() + 4 * lo, self.ms.data_ptr() + 4 * lo,
+                                              self.mom.data_ptr() + 4 * lo, grad.data_ptr(),
+                                              int(grad.dtype == torch.bfloat16), _lib.ptr(out_bf16), n,
+                                              self._hp_dev.data_ptr(), _lib.stream_ptr(self.w.device))
+            _lib.check(rc, "tony_rmsprop_step")
+            return
+        w, ms, mom = self.w[lo:lo + n], self.ms[lo:lo + n], self.mom[lo:lo + n]
+        g = grad.float() * self.grad_scale + self.weight_decay * w
+        ms.mul_(self.alpha).addcmul_(g, g, value=1 - self.alpha)
+        if self.tf_style:
+            mom.mul_(self.momentum).addcdiv_(g, (ms + self.eps).sqrt_(), value=self.lr)
+            w.sub_(mom)
+        else:
+            mom.mul_(self.momentum).addcdiv_(g, ms.sqrt().add_(self.eps))
+            w.add_(mom, alpha=-self.lr)
+        if out_bf16 is not None:
+            out_bf16.copy_(w)
+
+    def state_dict(self):
+        return {"kind": "rmsprop", "step": self.step_count, "square_avg": self.ms, "momentum_buffer": self.mom,
+                "tf_style": self.tf_style, "lr": self.lr}
+
+    def load_state_dict(self, sd):
+        if bool(sd.get("tf_style", self.tf_style)) != self.tf_style:
+            raise ValueError(f"RMSProp checkpoint has tf_style={sd['tf_style']}, this optimizer {self.tf_style}")
+        self.step_count = int(sd["step"])
+        self.ms.copy_(sd["square_avg"])
+        self.mom.copy_(sd["momentum_buffer"])
+        self.lr = float(sd.get("lr", self.lr))
+
+    def plane_state(self):
+        return 3, self.ms, self.mom
 
 
 def grad_stats(grad: torch.Tensor):

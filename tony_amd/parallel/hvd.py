@@ -323,6 +323,31 @@ def broadcast_optimizer_state(optimizer: torch.optim.Optimizer, root_rank: int =
         optimizer.load_state_dict(new)
 
 
+_NEEDS_SGD = "fused=True needs a single-group, dampening-free torch.optim.SGD on GPU tensors"
+
+
+def _fused_family(optimizer, groups):
+    """``fused=True`` with a torch Adam / AdamW / Adagrad / RMSprop: its kind ("adam", "adagrad", "rmsprop"), or
+    a ValueError naming what the fused HIP apply (ops/optim.py) cannot do.  Checked before any GPU call."""
+    name = type(optimizer).__name__
+    if len(optimizer.param_groups) != 1:
+        raise ValueError(_NEEDS_SGD)
+    g = optimizer.param_groups[0]
+    for key in ("amsgrad", "maximize", "centered", "capturable"):
+        if g.get(key, False):
+            raise ValueError(f"fused=True does not support torch.optim.{name}({key}=True)")
+    if g.get("lr_decay", 0):
+        raise ValueError(f"fused=True does not support torch.optim.{name} with lr_decay != 0")
+    if any(f.data.dtype != torch.float32 for f, _ in groups):
+        raise ValueError(f"fused=True with torch.optim.{name} needs fp32 parameters (a bf16 parameter would need a "
+                         "master copy kept in sync; use torch.optim.SGD for that)")
+    if any(f.device.type != "cuda" for f, _ in groups):
+        raise ValueError(_NEEDS_SGD)  # CPU tensors: nothing is fused, as before
+    if isinstance(optimizer, torch.optim.Adagrad):
+        return "adagrad"
+    return "rmsprop" if isinstance(optimizer, torch.optim.RMSprop) else "adam"
+
+
 class _DistributedOptimizer:
     """Wraps a torch optimizer: gradients are averaged (bucketed, overlapped) before ``step``.
 
@@ -372,11 +397,31 @@ class _DistributedOptimizer:
                     and all(f.device.type == "cuda" for f, _ in self.groups)
                     and not optimizer.param_groups[0].get("dampening", 0)
                     and not optimizer.param_groups[0].get("maximize", False))
+        # an explicit fused=True also takes a single-group Adam / AdamW / Adagrad / RMSprop over fp32 GPU
+        # parameters (the flat buffer is then the master: nothing to resync); fused=None auto-fuses SGD only
+        self._kind = "sgd"
         if fused is None:
             fused = can_fuse
         elif fused and not can_fuse:
-            raise ValueError("fused=True needs a single-group, dampening-free torch.optim.SGD on GPU tensors")
-        if fused:
+            if not isinstance(optimizer, (torch.optim.Adam, torch.optim.AdamW, torch.optim.Adagrad,
+                                          torch.optim.RMSprop)):
+                raise ValueError(_NEEDS_SGD)
+            self._kind = _fused_family(optimizer, self.groups)
+        if fused and self._kind != "sgd":
+            from ..ops.optim import FlatAdagrad, FlatAdam, FlatRMSProp
+
+            g = optimizer.param_groups[0]
+            for flat, _ in self.groups:
+                if self._kind == "adam":
+                    fo = FlatAdam(flat.data, float(g["lr"]))
+                elif self._kind == "adagrad":
+                    fo = FlatAdagrad(flat.data, float(g["lr"]),
+                                     initial_accumulator_value=g.get("initial_accumulator_value", 0.0))
+                else:
+                    fo = FlatRMSProp(flat.data, float(g["lr"]))
+                self._fused.append((flat, fo))
+            self._sync_hp()
+        elif fused:
             from ..ops.optim import FlatSGD
 
             g = optimizer.param_groups[0]
@@ -387,12 +432,36 @@ class _DistributedOptimizer:
                 self._fused.append((flat, FlatSGD(master, g["lr"], momentum=g["momentum"],
                                                   weight_decay=g["weight_decay"], nesterov=g["nesterov"],
                                                   resync=master is not flat.data)))
-            # torch-SGD state index of every parameter -> (flat buffer, slot)
+        if fused:
+            # torch state index of every parameter -> (flat buffer, slot)
             slot_of = {}
             for fi, (flat, _) in enumerate(self.groups):
                 for slot, p in zip(flat.slots, flat.params):
                     slot_of[id(p)] = (fi, slot)
             self._slots = [slot_of.get(id(p)) for p in optimizer.param_groups[0]["params"]]
+
+    def _sync_hp(self):
+        """Copy the wrapped Adam / Adagrad / RMSprop group (lr schedules edit it) into the flat optimizers."""
+        g = self.optimizer.param_groups[0]
+        for _, opt in self._fused:
+            opt.lr, opt.weight_decay = float(g["lr"]), float(g["weight_decay"])
+            if self._kind == "adam":
+                opt.b1, opt.b2 = float(g["betas"][0]), float(g["betas"][1])
+                opt.eps = float(g["eps"])
+                opt.decoupled = isinstance(self.optimizer, torch.optim.AdamW) or \
+                    bool(g.get("decoupled_weight_decay", False))
+            elif self._kind == "adagrad":
+                opt.eps = float(g["eps"])
+            else:
+                opt.alpha, opt.momentum, opt.eps = float(g["alpha"]), float(g["momentum"]), float(g["eps"])
+
+    def _state_tensors(self, opt) -> dict:
+        """torch's per-parameter state names of the wrapped Adam / Adagrad / RMSprop -> the flat state tensor."""
+        if self._kind == "adam":
+            return {"exp_avg": opt.m, "exp_avg_sq": opt.v}
+        if self._kind == "adagrad":
+            return {"sum": opt.h}
+        return {"square_avg": opt.ms, "momentum_buffer": opt.mom}
 
     # torch.optim.Optimizer surface
     @property
@@ -404,12 +473,29 @@ class _DistributedOptimizer:
         return self.optimizer.state
 
     def state_dict(self):
-        """torch.optim.SGD's state_dict format; with the fused apply the momentum buffers are views of
-        the flat fp32 momentum (the wrapped optimizer never steps, so its own state is empty)."""
+        """The wrapped torch class's state_dict format; with the fused apply the per-parameter state (SGD's
+        ``momentum_buffer``; ``step`` + ``exp_avg`` / ``exp_avg_sq``, ``sum``, ``square_avg`` / ``momentum_buffer``)
+        is built from views of the flat fp32 state (the wrapped optimizer never steps, so its own is unused)."""
         sd = self.optimizer.state_dict()
         if not self._fused:
             return sd
         state = {}
+        if self._kind != "sgd":
+            momentum = self.optimizer.param_groups[0].get("momentum", 0)
+            for i, fs in enumerate(self._slots):
+                if fs is None:  # a frozen parameter: no state
+                    continue
+                fi, slot = fs
+                opt = self._fused[fi][1]
+                if not opt.step_count and self._kind != "adagrad":  # torch creates these at the first step
+                    continue
+                st = {"step": torch.tensor(float(opt.step_count))}
+                for key, t in self._state_tensors(opt).items():
+                    if key != "momentum_buffer" or momentum:
+                        st[key] = slot.view(t).clone()
+                state[i] = st
+            sd["state"] = state
+            return sd
         for i, fs in enumerate(self._slots):
             if fs is None:  # a frozen parameter: no state
                 continue
@@ -425,6 +511,24 @@ class _DistributedOptimizer:
         if not self._fused:
             return
         g = self.optimizer.param_groups[0]
+        if self._kind != "sgd":
+            self._sync_hp()
+            for _, opt in self._fused:
+                opt.step_count = 0
+                for key, t in self._state_tensors(opt).items():
+                    t.fill_(float(g.get("initial_accumulator_value", 0.0)) if key == "sum" else 0.0)
+            for i, st in sd.get("state", {}).items():
+                fs = self._slots[int(i)]
+                if fs is None or not isinstance(st, dict):
+                    continue
+                fi, slot = fs
+                opt = self._fused[fi][1]
+                with torch.no_grad():
+                    for key, t in self._state_tensors(opt).items():
+                        if st.get(key) is not None:
+                            slot.view(t).copy_(st[key].to(device=t.device, dtype=torch.float32))
+                opt.step_count = max(opt.step_count, int(st.get("step", 0)))
+            return
         for fi, (_, opt) in enumerate(self._fused):
             opt.v.zero_()
             opt.lr, opt.momentum, opt.weight_decay = g["lr"], g["momentum"], g["weight_decay"]
@@ -454,6 +558,11 @@ class _DistributedOptimizer:
         if not self._fused:
             return self.optimizer.step(closure)
         loss = closure() if closure is not None else None
+        if self._kind != "sgd":
+            self._sync_hp()
+            for flat, opt in self._fused:
+                opt.step(flat.grad)  # fp32: the flat buffer is the master, updated in place
+            return loss
         g = self.optimizer.param_groups[0]  # lr schedules edit the wrapped optimizer's group
         for flat, opt in self._fused:
             opt.lr, opt.momentum, opt.weight_decay = g["lr"], g["momentum"], g["weight_decay"]
@@ -470,7 +579,8 @@ class _DistributedOptimizer:
 def DistributedOptimizer(optimizer, named_parameters=None, compression=Compression.none,  # noqa: N802
                          backward_passes_per_step: int = 1, op=Average, **kw):
     """Horovod's DistributedOptimizer: bucketed gradient averaging overlapped with backward; a plain
-    torch SGD on GPU tensors is applied by the fused HIP kernel (``fused=False`` keeps torch's)."""
+    torch SGD on GPU tensors is applied by the fused HIP kernel (``fused=False`` keeps torch's); ``fused=True``
+    also takes a single-group Adam / AdamW / Adagrad / RMSprop over fp32 GPU parameters."""
     return _DistributedOptimizer(optimizer, named_parameters, compression, backward_passes_per_step, op, **kw)
 
 

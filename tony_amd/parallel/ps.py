@@ -52,7 +52,7 @@ from typing import Dict, List, Optional
 import torch
 import torch.distributed as dist
 
-from ..ops.optim import FlatAdam, FlatSGD
+from ..ops.optim import FlatAdagrad, FlatAdam, FlatRMSProp, FlatSGD
 from . import collectives as coll
 from .buckets import DEFAULT_BUCKET_MB, Bucket, GradBucketEngine, make_buckets
 from .flat import FlatParams
@@ -60,12 +60,25 @@ from .flat import FlatParams
 
 def make_optimizer(kind: str, master: torch.Tensor, lr: float, momentum: float = 0.9, weight_decay: float = 0.0,
                    **kw):
+    """The flat optimizer of ``kind`` over ``master``: ``sgd`` / ``momentum``, ``adam`` / ``adamw``, ``adagrad``,
+    ``rmsprop`` (torch's form) and ``rmsprop_tf`` (TF's form, the Inception-v3 recipe).  ``momentum`` goes to SGD and
+    to both RMSProp kinds; ``eps``, ``alpha`` and ``initial_accumulator_value`` come from ``kw``.  ``rmsprop_tf``'s
+    ``eps`` defaults to 1.0, the Inception recipe's value (RMSProp decay 0.9, momentum 0.9, epsilon 1.0), so that
+    ``bench.py --optimizer rmsprop_tf``, which passes no ``eps``, trains with that recipe."""
     kind = kind.lower()
     if kind in ("sgd", "momentum"):
         return FlatSGD(master, lr, momentum=momentum, weight_decay=weight_decay, nesterov=kw.get("nesterov", False))
     if kind in ("adam", "adamw"):
         return FlatAdam(master, lr, betas=kw.get("betas", (0.9, 0.999)), eps=kw.get("eps", 1e-8),
                         weight_decay=weight_decay, decoupled=(kind == "adamw"))
+    if kind == "adagrad":
+        return FlatAdagrad(master, lr, eps=kw.get("eps", 1e-7),
+                           initial_accumulator_value=kw.get("initial_accumulator_value", 0.1),
+                           weight_decay=weight_decay)
+    if kind in ("rmsprop", "rmsprop_tf"):
+        tf_style = kind == "rmsprop_tf"
+        return FlatRMSProp(master, lr, alpha=kw.get("alpha", 0.9), momentum=momentum,
+                           eps=kw.get("eps", 1.0 if tf_style else 1e-8), weight_decay=weight_decay, tf_style=tf_style)
     raise ValueError(f"unknown optimizer {kind!r}")
 
 

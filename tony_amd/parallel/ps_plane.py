@@ -243,20 +243,16 @@ class XgmiPSPlane:
         self.pushed += b.numel * self.wesz
 
     def apply(self, b, step: int, opt, m: int, local_params: Optional[torch.Tensor] = None) -> None:
-        """PS: apply bucket b from the landed rows (``opt``: FlatSGD / FlatAdam over this ps's masters,
-        ``m``: the bucket's offset in them) and land the new variables in every worker's window."""
-        from ..ops.optim import FlatAdam
-
+        """PS: apply bucket b from the landed rows (``opt``: a flat optimizer of ops/optim.py over this ps's
+        masters, ``m``: the bucket's offset in them) and land the new variables in every worker's window."""
         if self.dead is not None:
             raise PSPlaneError(self.dead)
-        adam = isinstance(opt, FlatAdam)
-        s0 = opt.m if adam else opt.v
-        s1 = opt.v if adam else None
+        code, s0, s1 = opt.plane_state()
         stream = _lib.stream_ptr(self.device)
         rc = _lib.lib().tony_ps_apply(
             self.window, self.row_off[b.index], self.row_stride[self.rank], len(self.worker_ranks),
             int(self.wire_dtype == torch.bfloat16), b.numel, b.lo, opt.w.data_ptr() + 4 * m, s0.data_ptr() + 4 * m,
-            None if s1 is None else s1.data_ptr() + 4 * m, opt._hp_dev.data_ptr(), int(adam), self._worker_windows,
+            None if s1 is None else s1.data_ptr() + 4 * m, opt._hp_dev.data_ptr(), code, self._worker_windows,
             None if local_params is None else local_params.data_ptr(), int(self.flat.data.dtype == torch.bfloat16),
             b.index, (step + 1) & 0xFFFFFFFF, int(not self.sync), SPIN_S, self.blocks[b.index], stream)
         _lib.check(rc, "tony_ps_apply")
