@@ -32,6 +32,8 @@ def main(argv=None) -> int:
     ap.add_argument("--lr", type=float, default=0.001)
     ap.add_argument("--fused", action="store_true",
                     help="apply Adam with the fused HIP kernel over the flat parameter buffer (GPU ranks)")
+    ap.add_argument("--clip-norm", type=float, default=0.0,
+                    help="clip the averaged gradient by its global norm (0: off; needs --fused)")
     a = ap.parse_args(argv)
     hvd.init()
     dev = hvd.device()
@@ -39,7 +41,8 @@ def main(argv=None) -> int:
     model = mnist_model("hvd_cnn", seed=hvd.rank()).to(dev)
     opt = torch.optim.Adam(model.parameters(), lr=a.lr * hvd.size())
     opt = hvd.DistributedOptimizer(opt, named_parameters=model.named_parameters(),
-                                   fused=True if a.fused else None)
+                                   fused=True if a.fused else None,
+                                   clip_norm=a.clip_norm if a.clip_norm > 0 else None)
     hvd.broadcast_parameters(model.state_dict(), root_rank=0)
     hvd.broadcast_optimizer_state(opt, root_rank=0)
     x_all, y_all = synthetic_mnist(a.batch_size * hvd.size() * 4, seed=7, device=dev)

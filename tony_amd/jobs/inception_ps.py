@@ -72,6 +72,11 @@ def main(argv=None) -> int:
     ap.add_argument("--optimizer", default="sgd", choices=["sgd", "rmsprop_tf"],
                     help="sgd (default): momentum SGD; rmsprop_tf: the model's published recipe (RMSProp in TF's "
                          "form, decay 0.9, momentum 0.9, epsilon 1.0)")
+    ap.add_argument("--clip-norm", type=float, default=0.0,
+                    help="clip the averaged gradient by its global norm (0: off; the published recipe uses 2.0)")
+    ap.add_argument("--ema-decay", type=float, default=0.0,
+                    help="keep an exponential moving average of the variables on the ps and report the loss of one "
+                         "forward on it at the end (0: off; the published recipe uses 0.9999)")
     a = ap.parse_args(argv)
     tc = TFConfig.from_env()
     on_gpu = torch.cuda.is_available()
@@ -101,10 +106,18 @@ def main(argv=None) -> int:
         model = inception_v3(fused=False, seed=0, precision="fp32").to(dev).to(memory_format=torch.channels_last)
     else:
         model = cast_model(inception_v3(fused=on_gpu, seed=0), dtype, dev).to(memory_format=torch.channels_last)
+    # --optimizer rmsprop_tf --clip-norm 2 --ema-decay 0.9999 is the full published recipe.  The global norm and
+    # the EMA live on the collective data plane (the xGMI PS plane applies rows as they land: parallel/ps.py)
+    extras = {}
+    if a.clip_norm > 0 or a.ema_decay > 0:
+        extras = dict(clip_norm=a.clip_norm if a.clip_norm > 0 else None,
+                      ema_decay=a.ema_decay if a.ema_decay > 0 else None, plane="rccl")
+        if mode == "dedicated" and on_gpu:
+            log("--clip-norm / --ema-decay: the dedicated PS runs on the collective data plane (plane=rccl)")
     ps = ParameterServer(model, optimizer=a.optimizer, lr=0.045, momentum=0.9, weight_decay=4e-5, mode=mode,
                          ps_ranks=tc.ps_ranks if mode == "dedicated" else (0,), dtype=dtype, device=dev,
                          wire_dtype=torch.float32 if dtype == torch.float32 else None,
-                         sync=not (a.async_ps and mode == "dedicated"))
+                         sync=not (a.async_ps and mode == "dedicated"), **extras)
     if mode == "dedicated" and not ps.sync and ps.plane is None:
         raise SystemExit("--async needs the xGMI PS data plane (GPU ranks)")
 
@@ -160,6 +173,9 @@ def main(argv=None) -> int:
         if a.save_steps:
             save(total, force=True)
             ckpt.wait()
+        if ps.has_ema:
+            with ps.ema_weights():  # collective: the ps task hands its EMA shard to the workers' evaluation
+                pass
         if on_gpu:
             torch.cuda.synchronize()
         if ps.plane is not None:
@@ -202,6 +218,14 @@ def main(argv=None) -> int:
     if a.save_steps:
         save(total, force=True)
         ckpt.wait()
+    if ps.has_ema:
+        # one forward on the EMA of the variables (what the recipe evaluates).  Outside trainer.step the
+        # Trainer's weight caches are not active, so nothing reads a stale copy and nothing needs a refresh
+        model.eval()
+        with ps.ema_weights(), torch.no_grad():
+            ema_loss = float(loss_fn(model(x), y))
+        model.train()
+        log(f"loss on the EMA weights (decay {a.ema_decay}): {ema_loss:.4f} (last training loss {float(loss):.4f})")
     rate = torch.tensor([tp.rate() if timed else 0.0], dtype=torch.float64, device=dev if on_gpu else "cpu")
     dist.all_reduce(rate)
     workers = len(ps.worker_ranks)

@@ -90,6 +90,12 @@ _SIGNATURES = {
     "tony_adagrad_step": [c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_int64, c_void_p, c_void_p],
     "tony_rmsprop_step": [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_int64, c_void_p, c_void_p],
     "tony_grad_stats": [c_void_p, c_int, c_int64, c_void_p, c_void_p],
+    # global-norm clipping / non-finite skip / EMA (csrc/optim.hip): partials, ctl, and the apply of any kind
+    "tony_grad_sumsq_blocks": [],
+    "tony_grad_sumsq": [c_void_p, c_int, c_int64, c_void_p, c_void_p],
+    "tony_clip_ctl": [c_void_p, c_int, c_void_p, c_void_p, c_void_p],
+    "tony_optim_apply_x": [c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_int64,
+                           c_void_p, c_void_p, c_void_p, c_void_p],
     "tony_xent_fwd": [c_void_p, c_int, c_int64, c_int, c_int64, c_void_p, c_float, c_void_p, c_void_p, c_void_p],
     "tony_xent_bwd": [c_void_p, c_int, c_int64, c_int, c_int64, c_void_p, c_float, c_void_p, c_void_p, c_void_p,
                       c_int64, c_void_p],

@@ -198,6 +198,142 @@ int grid_for(int64_t n4) {
   return static_cast<int>(g < 1 ? 1 : g);
 }
 
+// -- global-norm clipping, non-finite step skip, EMA of the variables ------------------------------------
+// Three launches on one stream: grad_sumsq (one fp32 partial per workgroup of a FIXED grid, stored, so the
+// result does not depend on arrival order), clip_ctl (one workgroup folds the partials of every bucket into
+// ctl = [coef, skip, norm, skipped steps]) and apply_x (the update of `kind`, its gradient scale times coef,
+// nothing at all when skip is set, the EMA beside the master).
+//   xhp = [clip_norm, base_grad_scale, skip_nonfinite, ema_decay, 1 - ema_decay]   (host-pushed, like hp)
+constexpr int kSumsqGrid = 1024;  // workgroups of every grad_sumsq launch = floats of one partial block
+
+template <bool kGradBf16>
+__global__ __launch_bounds__(kThreads) void grad_sumsq_kernel(const void* __restrict__ g, int64_t n4,
+                                                              float* __restrict__ partials) {
+  __shared__ float part[kThreads / kWave];
+  float acc = 0.f;
+  const int64_t stride = static_cast<int64_t>(gridDim.x) * kThreads;
+#pragma unroll 4
+  for (int64_t q = static_cast<int64_t>(blockIdx.x) * kThreads + threadIdx.x; q < n4; q += stride) {
+    float gf[4];
+    load_grad4<kGradBf16>(g, q * 4, gf);
+#pragma unroll
+    for (int k = 0; k < 4; ++k) acc = fmaf(gf[k], gf[k], acc);
+  }
+  acc = wave_sum(acc);
+  const int lane = threadIdx.x & (kWave - 1), wid = threadIdx.x / kWave;
+  if (lane == 0) part[wid] = acc;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    float t = 0.f;
+    for (int k = 0; k < kThreads / kWave; ++k) t += part[k];
+    partials[blockIdx.x] = t;  // a workgroup past the end of the gradient stores its 0
+  }
+}
+
+// S = sum of the partials in index order (each thread a contiguous run, the runs in thread order), in double.
+__global__ __launch_bounds__(kThreads) void clip_ctl_kernel(const float* __restrict__ partials, int n,
+                                                            const float* __restrict__ xhp,
+                                                            float* __restrict__ ctl) {
+  __shared__ double run[kThreads];
+  const int per = (n + kThreads - 1) / kThreads;
+  const int lo = threadIdx.x * per;
+  const int hi = lo + per < n ? lo + per : n;
+  double s = 0.0;
+  for (int i = lo; i < hi; ++i) s += static_cast<double>(partials[i]);
+  run[threadIdx.x] = s;
+  __syncthreads();
+  if (threadIdx.x != 0) return;
+  double S = 0.0;
+  for (int k = 0; k < kThreads; ++k) S += run[k];
+  const float clip = xhp[0], gs = xhp[1];
+  const bool skip = xhp[2] != 0.f && !isfinite(S);
+  const float norm = static_cast<float>(static_cast<double>(gs) * sqrt(S));
+  // tf.clip_by_global_norm: exactly 1 when nothing clips, no epsilon
+  const float coef = clip > 0.f ? clip / fmaxf(norm, clip) : 1.f;
+  ctl[0] = coef;
+  ctl[1] = skip ? 1.f : 0.f;
+  ctl[2] = norm;
+  if (skip) ctl[3] += 1.f;
+}
+
+__device__ __forceinline__ void load4(const float* p, float* f) {
+  const float4 v = *reinterpret_cast<const float4*>(p);
+  f[0] = v.x;
+  f[1] = v.y;
+  f[2] = v.z;
+  f[3] = v.w;
+}
+
+__device__ __forceinline__ void store4(float* p, const float* f) {
+  *reinterpret_cast<float4*>(p) = make_float4(f[0], f[1], f[2], f[3]);
+}
+
+// kKind: 0 SGD (s0 = v), 1 Adam (m, v), 2 Adagrad (h), 3 RMSProp (ms, mom) -- the codes of plane_state().
+template <int kKind, bool kGradBf16>
+__global__ __launch_bounds__(kThreads) void apply_x_kernel(float* __restrict__ w, float* __restrict__ s0,
+                                                           float* __restrict__ s1, float* __restrict__ ema,
+                                                           const void* __restrict__ g,
+                                                           uint16_t* __restrict__ w_bf16, int64_t n4,
+                                                           const float* __restrict__ hp,
+                                                           const float* __restrict__ xhp,
+                                                           const float* __restrict__ ctl) {
+  float coef = 1.f;
+  if (ctl != nullptr) {
+    if (ctl[1] != 0.f) return;  // a skipped step touches nothing
+    coef = ctl[0];
+  }
+  const float omd = ema != nullptr ? xhp[4] : 0.f;
+  constexpr bool kTwo = kKind == 1 || kKind == 3;
+  const bool resync = kKind == 0 && hp[5] != 0.f && w_bf16 != nullptr;
+  const int64_t stride = static_cast<int64_t>(gridDim.x) * kThreads;
+  for (int64_t q = static_cast<int64_t>(blockIdx.x) * kThreads + threadIdx.x; q < n4; q += stride) {
+    const int64_t i = q * 4;
+    float gf[4], wf[4], af[4], bf[4];
+    load_grad4<kGradBf16>(g, i, gf);
+    load4(w + i, wf);
+    load4(s0 + i, af);
+    if constexpr (kTwo) load4(s1 + i, bf);
+    if constexpr (kKind == 0) {
+      if (resync) {
+        const uint2 cv = *reinterpret_cast<const uint2*>(w_bf16 + i);
+        const uint16_t cur[4] = {static_cast<uint16_t>(cv.x & 0xffffu), static_cast<uint16_t>(cv.x >> 16),
+                                 static_cast<uint16_t>(cv.y & 0xffffu), static_cast<uint16_t>(cv.y >> 16)};
+#pragma unroll
+        for (int k = 0; k < 4; ++k)
+          if (cur[k] != f2bf(wf[k])) wf[k] = bf2f(cur[k]);
+      }
+      sgd_update4(wf, af, gf, hp[0], hp[1], hp[2], hp[3] * coef, hp[4] != 0.f);
+    } else if constexpr (kKind == 1) {
+      const float lr = hp[0];
+      adam_update4(wf, af, bf, gf, lr, hp[1], hp[2], hp[3], hp[4], hp[5] * coef, lr / hp[6], rsqrtf(hp[7]),
+                   hp[8] != 0.f);
+    } else if constexpr (kKind == 2) {
+      adagrad_update4(wf, af, gf, hp[0], hp[1], hp[2], hp[3] * coef);
+    } else {
+      rmsprop_update4(wf, af, bf, gf, hp[0], hp[1], hp[2], hp[3], hp[4], hp[5] * coef, hp[6] != 0.f);
+    }
+    store4(w + i, wf);
+    store4(s0 + i, af);
+    if constexpr (kTwo) store4(s1 + i, bf);
+    if (ema != nullptr) {
+      float ef[4];
+      load4(ema + i, ef);
+      ema_update4(ef, wf, omd);
+      store4(ema + i, ef);
+    }
+    if (w_bf16 != nullptr) store_bf16x4(w_bf16 + i, wf);
+  }
+}
+
+template <int kKind>
+void launch_apply_x(float* w, float* s0, float* s1, float* ema, const void* g, int grad_bf16, uint16_t* w_bf16,
+                    int64_t n4, const float* hp, const float* xhp, const float* ctl, hipStream_t stream) {
+  if (grad_bf16)
+    apply_x_kernel<kKind, true><<<grid_for(n4), kThreads, 0, stream>>>(w, s0, s1, ema, g, w_bf16, n4, hp, xhp, ctl);
+  else
+    apply_x_kernel<kKind, false><<<grid_for(n4), kThreads, 0, stream>>>(w, s0, s1, ema, g, w_bf16, n4, hp, xhp, ctl);
+}
+
 }  // namespace
 
 // n must be a multiple of 4 (flat buffers are padded by the caller).
@@ -258,6 +394,52 @@ TONY_API int tony_grad_stats(const void* g, int grad_bf16, int64_t n, float* out
     grad_stats_kernel<true><<<grid, kThreads, 0, stream>>>(g, n4, out);
   else
     grad_stats_kernel<false><<<grid, kThreads, 0, stream>>>(g, n4, out);
+  TONY_LAUNCH_CHECK();
+  return 0;
+}
+
+// Floats of one partial block: every tony_grad_sumsq launch stores exactly this many.
+TONY_API int tony_grad_sumsq_blocks() { return kSumsqGrid; }
+
+// partials[0 .. kSumsqGrid) = per-workgroup sums of g^2, in a fixed order (no atomics: bit-reproducible).
+TONY_API int tony_grad_sumsq(const void* g, int grad_bf16, int64_t n, float* partials, hipStream_t stream) {
+  if (n % 4 || n < 0) return -1;
+  const int64_t n4 = n / 4;
+  if (grad_bf16)
+    grad_sumsq_kernel<true><<<kSumsqGrid, kThreads, 0, stream>>>(g, n4, partials);
+  else
+    grad_sumsq_kernel<false><<<kSumsqGrid, kThreads, 0, stream>>>(g, n4, partials);
+  TONY_LAUNCH_CHECK();
+  return 0;
+}
+
+// ctl = [coef, skip, norm, skipped steps (+= skip)] from the partial blocks of every bucket, laid end to end.
+TONY_API int tony_clip_ctl(const float* partials, int n_partials, const float* xhp, float* ctl,
+                           hipStream_t stream) {
+  if (n_partials < 0) return -1;
+  clip_ctl_kernel<<<1, kThreads, 0, stream>>>(partials, n_partials, xhp, ctl);
+  TONY_LAUNCH_CHECK();
+  return 0;
+}
+
+// The update of `kind` (0 SGD, 1 Adam, 2 Adagrad, 3 RMSProp; hp in that kind's layout above) with the gradient
+// scale times ctl[0], nothing at all when ctl[1] is set, and ema += xhp[4] (w_new - ema) when ema is given.
+// ctl == nullptr: coef 1, no skip.  s1 is ignored by the one-state kinds.
+TONY_API int tony_optim_apply_x(int kind, float* w, float* s0, float* s1, float* ema, const void* g, int grad_bf16,
+                                void* w_bf16, int64_t n, const float* hp, const float* xhp, const float* ctl,
+                                hipStream_t stream) {
+  if (n % 4 || n < 0) return -1;
+  if (ema != nullptr && xhp == nullptr) return -2;
+  if ((kind == 1 || kind == 3) && s1 == nullptr) return -3;
+  const int64_t n4 = n / 4;
+  uint16_t* out = static_cast<uint16_t*>(w_bf16);
+  switch (kind) {
+    case 0: launch_apply_x<0>(w, s0, s1, ema, g, grad_bf16, out, n4, hp, xhp, ctl, stream); break;
+    case 1: launch_apply_x<1>(w, s0, s1, ema, g, grad_bf16, out, n4, hp, xhp, ctl, stream); break;
+    case 2: launch_apply_x<2>(w, s0, s1, ema, g, grad_bf16, out, n4, hp, xhp, ctl, stream); break;
+    case 3: launch_apply_x<3>(w, s0, s1, ema, g, grad_bf16, out, n4, hp, xhp, ctl, stream); break;
+    default: return -4;
+  }
   TONY_LAUNCH_CHECK();
   return 0;
 }

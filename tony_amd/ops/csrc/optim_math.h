@@ -68,4 +68,10 @@ __device__ __forceinline__ void rmsprop_update4(float* wf, float* sf, float* mf,
   }
 }
 
+// ema += (1 - d) (w - ema)   (tf.train.ExponentialMovingAverage.apply; omd = 1 - d, formed on the host in double)
+__device__ __forceinline__ void ema_update4(float* ef, const float* wf, float omd) {
+#pragma unroll
+  for (int k = 0; k < 4; ++k) ef[k] = fmaf(omd, wf[k] - ef[k], ef[k]);
+}
+
 }  // namespace tony

@@ -8,6 +8,10 @@ is computed with PyTorch ops (used by the CPU test-suite and local mode).
 
 Hyper-parameters are kept in a device tensor that is refreshed (a 36-byte H2D
 copy) before each step, so a captured HIP graph sees the current lr / step.
+
+Every kind also takes ``clip_norm`` (clipping by the global gradient norm), ``skip_nonfinite`` and ``ema_decay`` /
+``ema_warmup`` (an EMA of the variables beside the master): see ``_FlatOptimizer``.  The norm, the clip
+coefficient and the skip decision stay on the device, so these too replay from a captured graph.
 """
 from __future__ import annotations
 
@@ -16,14 +20,45 @@ import torch
 from . import _lib
 
 
+SUMSQ_BLOCKS = 1024  # floats of one partial block of tony_grad_sumsq (csrc/optim.hip kSumsqGrid; checked on use)
+N_XHP = 8            # xhp = [clip_norm, base_grad_scale, skip_nonfinite, ema_decay, 1 - ema_decay, 0, 0, 0]
+
+
+def _f32(x: float) -> float:
+    """``x`` rounded to fp32 (the CPU fallbacks form the clip coefficient in the kernels' precision)."""
+    return torch.tensor(float(x), dtype=torch.float32).item()
+
+
 class _FlatOptimizer:
+    """Common part of the flat optimizers.  Beyond the update itself every kind takes
+
+    ``clip_norm``       clip the averaged gradient by its global L2 norm (``tf.clip_by_global_norm``: the
+                        gradient is scaled by ``clip_norm / max(norm, clip_norm)``, before weight decay is added);
+    ``skip_nonfinite``  a step whose gradient holds an inf / nan (or whose sum of squares overflows fp32) changes
+                        nothing; the skip is decided on the device, so the host's step counter still advances;
+    ``ema_decay``       keep ``ema += (1 - d)(w - ema)`` beside the master (``tf.train.ExponentialMovingAverage``,
+                        the shadow starts as a copy of the master); ``ema_warmup`` uses TF's ``num_updates`` form
+                        ``d = min(ema_decay, (1 + t) / (10 + t))`` with t the step being applied.
+
+    With all four at their defaults nothing is allocated and ``apply_range`` launches the plain kernel of its
+    kind.  Otherwise the norm takes two small launches before the apply (``accumulate_sumsq`` once per bucket,
+    ``finish_norm`` once per step: csrc/optim.hip tony_grad_sumsq / tony_clip_ctl) and the apply is
+    ``tony_optim_apply_x``, which reads the coefficient and the skip flag on the device."""
+
     n_hp = 0
 
-    def __init__(self, master: torch.Tensor, lr: float, weight_decay: float = 0.0):
+    def __init__(self, master: torch.Tensor, lr: float, weight_decay: float = 0.0, clip_norm=None,
+                 skip_nonfinite: bool = False, ema_decay=None, ema_warmup: bool = False):
         if master.dtype != torch.float32 or master.dim() != 1:
             raise TypeError("master shard must be a flat fp32 tensor")
         if master.numel() % 4:
             raise ValueError("flat shard length must be a multiple of 4 (pad the buffer)")
+        if clip_norm is not None and not float(clip_norm) > 0.0:
+            raise ValueError(f"clip_norm must be positive (None: no clipping), got {clip_norm}")
+        if ema_decay is not None and not 0.0 <= float(ema_decay) < 1.0:
+            raise ValueError(f"ema_decay must be in [0, 1) (None: no EMA), got {ema_decay}")
+        if ema_warmup and ema_decay is None:
+            raise ValueError("ema_warmup needs ema_decay")
         self.w = master
         self.lr = float(lr)
         self.weight_decay = float(weight_decay)
@@ -32,6 +67,147 @@ class _FlatOptimizer:
         dev = master.device
         self._hp_last = None
         self._hp_dev = torch.zeros(self.n_hp, dtype=torch.float32, device=dev)
+        self.clip_norm = None if clip_norm is None else float(clip_norm)
+        self.skip_nonfinite = bool(skip_nonfinite)
+        self.ema_decay = None if ema_decay is None else float(ema_decay)
+        self.ema_warmup = bool(ema_warmup)
+        self.needs_norm = self.clip_norm is not None or self.skip_nonfinite
+        self._extended = self.needs_norm or self.ema_decay is not None
+        self.ema = self._xhp_dev = self._xhp_last = self._ctl = self._partials = None
+        if self._extended:
+            self._xhp_dev = torch.zeros(N_XHP, dtype=torch.float32, device=dev)
+            self._ctl = torch.zeros(4, dtype=torch.float32, device=dev)
+            self._ctl[0] = 1.0  # [coef, skip, norm, skipped steps]
+            if self.ema_decay is not None:
+                self.ema = master.detach().clone()
+            if dev.type == "cuda" and _lib.lib().tony_grad_sumsq_blocks() != SUMSQ_BLOCKS:
+                raise _lib.KernelError(f"{_lib.SO_PATH} stores {_lib.lib().tony_grad_sumsq_blocks()} partials per "
+                                       f"sum-of-squares launch, the Python side expects {SUMSQ_BLOCKS}: rebuild")
+
+    # -- clipping / skip / EMA ------------------------------------------------------------------------------
+    def _ema_decay_now(self) -> float:
+        d = self.ema_decay
+        if self.ema_warmup:
+            t = self.step_count
+            d = min(d, (1.0 + t) / (10.0 + t))
+        return d
+
+    def _xhp_values(self):
+        d = self._ema_decay_now() if self.ema_decay is not None else 0.0
+        return [self.clip_norm or 0.0, self.grad_scale, 1.0 if self.skip_nonfinite else 0.0, d, 1.0 - d, 0.0, 0.0,
+                0.0]
+
+    def partials(self, n_slots: int = 1) -> torch.Tensor:
+        """The ``n_slots`` partial blocks (``SUMSQ_BLOCKS`` floats each, zero until accumulated into) that
+        ``finish_norm(n_slots)`` folds; a sharded PS all-reduces them between the two."""
+        if not self.needs_norm:
+            raise RuntimeError("the gradient norm needs clip_norm or skip_nonfinite")
+        if self._partials is None or self._partials.numel() < n_slots * SUMSQ_BLOCKS:
+            if self.w.is_cuda and torch.cuda.is_current_stream_capturing():
+                raise RuntimeError("partial blocks must exist before a graph capture: call partials(n_slots) first")
+            old = self._partials
+            self._partials = torch.zeros(n_slots * SUMSQ_BLOCKS, dtype=torch.float32, device=self.w.device)
+            if old is not None:
+                self._partials[:old.numel()].copy_(old)
+        return self._partials[:n_slots * SUMSQ_BLOCKS]
+
+    def share_partials(self, other: "_FlatOptimizer", n_slots: int):
+        """Use ``other``'s partial blocks: several optimizers (one per dtype group) then accumulate into their own
+        slot of one buffer and each ``finish_norm(n_slots)`` sees the norm over all of them."""
+        self._partials = other.partials(n_slots)
+
+    def accumulate_sumsq(self, grad: torch.Tensor, slot: int = 0):
+        """Partial block ``slot`` = the sum of squares of ``grad`` (a whole flat gradient, or one bucket's piece
+        of it), in a fixed order: the same gradient gives the same bits."""
+        if grad.numel() % 4:
+            raise ValueError("gradient length must be a multiple of 4")
+        blk = self.partials(slot + 1)[slot * SUMSQ_BLOCKS:]
+        if self.w.is_cuda:
+            rc = _lib.lib().tony_grad_sumsq(grad.data_ptr(), int(grad.dtype == torch.bfloat16), grad.numel(),
+                                            blk.data_ptr(), _lib.stream_ptr(self.w.device))
+            _lib.check(rc, "tony_grad_sumsq")
+            return
+        blk.zero_()
+        blk[0] = grad.double().square().sum().float()
+
+    def finish_norm(self, n_slots: int = 1):
+        """Fold partial blocks [0, n_slots) into ``[coef, skip, norm, skipped steps]`` for the applies that follow."""
+        part = self.partials(n_slots)
+        if self.w.is_cuda:
+            rc = _lib.lib().tony_clip_ctl(part.data_ptr(), part.numel(), self._xhp_dev.data_ptr(),
+                                          self._ctl.data_ptr(), _lib.stream_ptr(self.w.device))
+            _lib.check(rc, "tony_clip_ctl")
+            return
+        S = part.double().sum().item()
+        finite = S == S and S != float("inf")
+        clip, gs = _f32(self.clip_norm or 0.0), _f32(self.grad_scale)
+        norm = _f32(gs * S ** 0.5) if finite else (float("nan") if S != S else float("inf"))
+        skip = self.skip_nonfinite and not finite
+        big = clip if not norm > clip else norm  # fmaxf: a nan norm gives clip
+        self._ctl[0] = _f32(clip / big) if clip > 0.0 else 1.0
+        self._ctl[1] = 1.0 if skip else 0.0
+        self._ctl[2] = norm
+        if skip:
+            self._ctl[3] += 1.0
+
+    def last_norm(self) -> float:
+        """The global gradient norm of the last ``finish_norm`` (synchronises: logging and tests only)."""
+        return float(self._ctl[2].item()) if self._ctl is not None else float("nan")
+
+    def skipped_steps(self) -> int:
+        """Steps skipped for a non-finite gradient so far (synchronises: logging and tests only)."""
+        return int(self._ctl[3].item()) if self._ctl is not None else 0
+
+    def _apply_x(self, grad: torch.Tensor, lo: int, out_bf16):
+        """``apply_range`` with clipping / skip / EMA: tony_optim_apply_x, or the same on CPU tensors."""
+        n = grad.numel()
+        if self.w.is_cuda:
+            kind, s0, s1 = self.plane_state()
+            rc = _lib.lib().tony_optim_apply_x(
+                kind, self.w.data_ptr() + 4 * lo, s0.data_ptr() + 4 * lo, 0 if s1 is None else s1.data_ptr() + 4 * lo,
+                0 if self.ema is None else self.ema.data_ptr() + 4 * lo, grad.data_ptr(),
+                int(grad.dtype == torch.bfloat16), _lib.ptr(out_bf16), n, self._hp_dev.data_ptr(),
+                self._xhp_dev.data_ptr(), self._ctl.data_ptr() if self.needs_norm else 0,
+                _lib.stream_ptr(self.w.device))
+            _lib.check(rc, "tony_optim_apply_x")
+            return
+        if self.needs_norm and self._ctl[1].item() != 0.0:
+            return  # skipped: nothing changes
+        gs = self.grad_scale
+        if self.needs_norm:
+            self.grad_scale = _f32(_f32(gs) * self._ctl[0].item())
+        try:
+            self._apply_cpu(grad, lo, out_bf16)
+        finally:
+            self.grad_scale = gs
+        if self.ema is not None:
+            e = self.ema[lo:lo + n]
+            e.add_((self.w[lo:lo + n] - e) * (1.0 - self._ema_decay_now()))
+
+    def _extras_state(self, sd: dict) -> dict:
+        if self.ema is not None:
+            sd["ema"] = self.ema
+        if self._extended:
+            sd["skipped"] = self.skipped_steps()
+        return sd
+
+    def _load_extras(self, sd: dict):
+        """After the masters are restored: the EMA and the skipped-step count of a checkpoint.  One written
+        without an EMA re-seeds it from the master (with a warning); one with an EMA needs ``ema_decay`` here."""
+        if sd.get("ema") is not None and self.ema is None:
+            raise ValueError("the checkpoint holds an EMA of the variables, this optimizer keeps none: "
+                             "construct it with ema_decay")
+        if self.ema is not None:
+            if sd.get("ema") is None:
+                import warnings
+
+                warnings.warn("optimizer checkpoint without an EMA of the variables: re-seeding it from the master",
+                              RuntimeWarning)
+                self.ema.copy_(self.w)
+            else:
+                self.ema.copy_(sd["ema"])
+        if self._ctl is not None:
+            self._ctl[3] = float(sd.get("skipped", 0))
 
     def _hp_values(self):
         raise NotImplementedError
@@ -39,6 +215,11 @@ class _FlatOptimizer:
     def _push_hp(self):
         if self.w.is_cuda and torch.cuda.is_current_stream_capturing():
             return  # graph capture: the Trainer refreshes hp before every replay
+        if self._extended:
+            xvals = [float(v) for v in self._xhp_values()]
+            if xvals != self._xhp_last:
+                self._xhp_dev.copy_(torch.tensor(xvals, dtype=torch.float32), non_blocking=True)
+                self._xhp_last = xvals
         vals = [float(v) for v in self._hp_values()]
         if vals == self._hp_last:
             return  # unchanged (constant-lr SGD): no H2D traffic at all
@@ -57,10 +238,14 @@ class _FlatOptimizer:
         raise NotImplementedError
 
     def step(self, grad: torch.Tensor, out_bf16: torch.Tensor | None = None):
-        """One whole-shard update: ``begin_step`` + ``apply_range`` over every element."""
+        """One whole-shard update: ``begin_step`` + ``apply_range`` over every element (with ``clip_norm`` or
+        ``skip_nonfinite``: the norm of ``grad`` first)."""
         if grad.numel() != self.w.numel():
             raise ValueError("grad / shard size mismatch")
         self.begin_step()
+        if self.needs_norm:
+            self.accumulate_sumsq(grad, 0)
+            self.finish_norm(1)
         self.apply_range(grad, 0, out_bf16)
 
     def state_dict(self):
@@ -77,8 +262,8 @@ class FlatSGD(_FlatOptimizer):
 
     n_hp = 6
 
-    def __init__(self, master, lr, momentum=0.9, weight_decay=0.0, nesterov=False, resync=False):
-        super().__init__(master, lr, weight_decay)
+    def __init__(self, master, lr, momentum=0.9, weight_decay=0.0, nesterov=False, resync=False, **extra):
+        super().__init__(master, lr, weight_decay, **extra)
         self.momentum = float(momentum)
         self.nesterov = bool(nesterov)
         # resync: the bf16 compute copy (``out_bf16``) is the parameters users see and may overwrite
@@ -97,12 +282,18 @@ class FlatSGD(_FlatOptimizer):
         n = grad.numel()
         if lo < 0 or lo + n > self.w.numel() or lo % 4 or n % 4:
             raise ValueError(f"range [{lo}, {lo + n}) outside the {self.w.numel()}-element shard or not 4-aligned")
+        if self._extended:
+            return self._apply_x(grad, lo, out_bf16)
         if self.w.is_cuda:
             rc = _lib.lib().tony_sgd_step(self.w.data_ptr() + 4 * lo, self.v.data_ptr() + 4 * lo, grad.data_ptr(),
                                           int(grad.dtype == torch.bfloat16), _lib.ptr(out_bf16), n,
                                           self._hp_dev.data_ptr(), _lib.stream_ptr(self.w.device))
             _lib.check(rc, "tony_sgd_step")
             return
+        self._apply_cpu(grad, lo, out_bf16)
+
+    def _apply_cpu(self, grad, lo, out_bf16):
+        n = grad.numel()
         w, v = self.w[lo:lo + n], self.v[lo:lo + n]
         if self.resync and out_bf16 is not None:
             changed = out_bf16 != w.to(out_bf16.dtype)
@@ -115,12 +306,13 @@ class FlatSGD(_FlatOptimizer):
             out_bf16.copy_(w)
 
     def state_dict(self):
-        return {"kind": "sgd", "step": self.step_count, "momentum_buffer": self.v, "lr": self.lr}
+        return self._extras_state({"kind": "sgd", "step": self.step_count, "momentum_buffer": self.v, "lr": self.lr})
 
     def load_state_dict(self, sd):
         self.step_count = int(sd["step"])
         self.v.copy_(sd["momentum_buffer"])
         self.lr = float(sd.get("lr", self.lr))
+        self._load_extras(sd)
 
     def plane_state(self):
         return 0, self.v, None
@@ -131,8 +323,8 @@ class FlatAdam(_FlatOptimizer):
 
     n_hp = 9
 
-    def __init__(self, master, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, decoupled=False):
-        super().__init__(master, lr, weight_decay)
+    def __init__(self, master, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, decoupled=False, **extra):
+        super().__init__(master, lr, weight_decay, **extra)
         self.b1, self.b2 = float(betas[0]), float(betas[1])
         self.eps = float(eps)
         self.decoupled = bool(decoupled)
@@ -148,6 +340,8 @@ class FlatAdam(_FlatOptimizer):
         n = grad.numel()
         if lo < 0 or lo + n > self.w.numel() or lo % 4 or n % 4:
             raise ValueError(f"range [{lo}, {lo + n}) outside the {self.w.numel()}-element shard or not 4-aligned")
+        if self._extended:
+            return self._apply_x(grad, lo, out_bf16)
         if self.w.is_cuda:
             rc = _lib.lib().tony_adam_step(self.w.data_ptr() + 4 * lo, self.m.data_ptr() + 4 * lo,
                                            self.v.data_ptr() + 4 * lo, grad.data_ptr(),
@@ -155,6 +349,10 @@ class FlatAdam(_FlatOptimizer):
                                            self._hp_dev.data_ptr(), _lib.stream_ptr(self.w.device))
             _lib.check(rc, "tony_adam_step")
             return
+        self._apply_cpu(grad, lo, out_bf16)
+
+    def _apply_cpu(self, grad, lo, out_bf16):
+        n = grad.numel()
         t = self.step_count
         w, m, v = self.w[lo:lo + n], self.m[lo:lo + n], self.v[lo:lo + n]
         g = grad.float() * self.grad_scale
@@ -170,13 +368,15 @@ class FlatAdam(_FlatOptimizer):
             out_bf16.copy_(w)
 
     def state_dict(self):
-        return {"kind": "adam", "step": self.step_count, "exp_avg": self.m, "exp_avg_sq": self.v, "lr": self.lr}
+        return self._extras_state({"kind": "adam", "step": self.step_count, "exp_avg": self.m, "exp_avg_sq": self.v,
+                                   "lr": self.lr})
 
     def load_state_dict(self, sd):
         self.step_count = int(sd["step"])
         self.m.copy_(sd["exp_avg"])
         self.v.copy_(sd["exp_avg_sq"])
         self.lr = float(sd.get("lr", self.lr))
+        self._load_extras(sd)
 
     def plane_state(self):
         return 1, self.m, self.v
@@ -188,8 +388,8 @@ class FlatAdagrad(_FlatOptimizer):
 
     n_hp = 4
 
-    def __init__(self, master, lr, eps=1e-7, initial_accumulator_value=0.1, weight_decay=0.0):
-        super().__init__(master, lr, weight_decay)
+    def __init__(self, master, lr, eps=1e-7, initial_accumulator_value=0.1, weight_decay=0.0, **extra):
+        super().__init__(master, lr, weight_decay, **extra)
         self.eps = float(eps)
         self.h = torch.full_like(master, float(initial_accumulator_value))
 
@@ -200,6 +400,8 @@ class FlatAdagrad(_FlatOptimizer):
         n = grad.numel()
         if lo < 0 or lo + n > self.w.numel() or lo % 4 or n % 4:
             raise ValueError(f"range [{lo}, {lo + n}) outside the {self.w.numel()}-element shard or not 4-aligned")
+        if self._extended:
+            return self._apply_x(grad, lo, out_bf16)
         if self.w.is_cuda:
             rc = _lib.lib().tony_adagrad_step(self.w.data_ptr() + 4 * lo, self.h.data_ptr() + 4 * lo,
                                               grad.data_ptr(), int(grad.dtype == torch.bfloat16),
@@ -207,6 +409,10 @@ class FlatAdagrad(_FlatOptimizer):
                                               _lib.stream_ptr(self.w.device))
             _lib.check(rc, "tony_adagrad_step")
             return
+        self._apply_cpu(grad, lo, out_bf16)
+
+    def _apply_cpu(self, grad, lo, out_bf16):
+        n = grad.numel()
         w, h = self.w[lo:lo + n], self.h[lo:lo + n]
         g = grad.float() * self.grad_scale + self.weight_decay * w
         h.addcmul_(g, g)
@@ -215,12 +421,13 @@ class FlatAdagrad(_FlatOptimizer):
             out_bf16.copy_(w)
 
     def state_dict(self):
-        return {"kind": "adagrad", "step": self.step_count, "sum": self.h, "lr": self.lr}
+        return self._extras_state({"kind": "adagrad", "step": self.step_count, "sum": self.h, "lr": self.lr})
 
     def load_state_dict(self, sd):
         self.step_count = int(sd["step"])
         self.h.copy_(sd["sum"])
         self.lr = float(sd.get("lr", self.lr))
+        self._load_extras(sd)
 
     def plane_state(self):
         return 2, self.h, None
@@ -238,8 +445,8 @@ class FlatRMSProp(_FlatOptimizer):
 
     n_hp = 7
 
-    def __init__(self, master, lr, alpha=0.9, momentum=0.0, eps=1e-8, weight_decay=0.0, tf_style=False):
-        super().__init__(master, lr, weight_decay)
+    def __init__(self, master, lr, alpha=0.9, momentum=0.0, eps=1e-8, weight_decay=0.0, tf_style=False, **extra):
+        super().__init__(master, lr, weight_decay, **extra)
         self.alpha = float(alpha)
         self.momentum = float(momentum)
         self.eps = float(eps)
@@ -255,6 +462,8 @@ class FlatRMSProp(_FlatOptimizer):
         n = grad.numel()
         if lo < 0 or lo + n > self.w.numel() or lo % 4 or n % 4:
             raise ValueError(f"range [{lo}, {lo + n}) outside the {self.w.numel()}-element shard or not 4-aligned")
+        if self._extended:
+            return self._apply_x(grad, lo, out_bf16)
         if self.w.is_cuda:
             rc = _lib.lib().tony_rmsprop_step(self.w.data_ptr() + 4 * lo, self.ms.data_ptr() + 4 * lo,
                                               self.mom.data_ptr() + 4 * lo, grad.data_ptr(),
@@ -262,6 +471,10 @@ class FlatRMSProp(_FlatOptimizer):
                                               self._hp_dev.data_ptr(), _lib.stream_ptr(self.w.device))
             _lib.check(rc, "tony_rmsprop_step")
             return
+        self._apply_cpu(grad, lo, out_bf16)
+
+    def _apply_cpu(self, grad, lo, out_bf16):
+        n = grad.numel()
         w, ms, mom = self.w[lo:lo + n], self.ms[lo:lo + n], self.mom[lo:lo + n]
         g = grad.float() * self.grad_scale + self.weight_decay * w
         ms.mul_(self.alpha).addcmul_(g, g, value=1 - self.alpha)
@@ -275,8 +488,8 @@ class FlatRMSProp(_FlatOptimizer):
             out_bf16.copy_(w)
 
     def state_dict(self):
-        return {"kind": "rmsprop", "step": self.step_count, "square_avg": self.ms, "momentum_buffer": self.mom,
-                "tf_style": self.tf_style, "lr": self.lr}
+        return self._extras_state({"kind": "rmsprop", "step": self.step_count, "square_avg": self.ms,
+                                   "momentum_buffer": self.mom, "tf_style": self.tf_style, "lr": self.lr})
 
     def load_state_dict(self, sd):
         if bool(sd.get("tf_style", self.tf_style)) != self.tf_style:
@@ -285,6 +498,7 @@ class FlatRMSProp(_FlatOptimizer):
         self.ms.copy_(sd["square_avg"])
         self.mom.copy_(sd["momentum_buffer"])
         self.lr = float(sd.get("lr", self.lr))
+        self._load_extras(sd)
 
     def plane_state(self):
         return 3, self.ms, self.mom

@@ -323,6 +323,8 @@ def broadcast_optimizer_state(optimizer: torch.optim.Optimizer, root_rank: int =
         optimizer.load_state_dict(new)
 
 
+_CLIP_NEEDS_FUSED = ("clip_norm is applied by the fused HIP optimizers only: pass fused=True (a single-group SGD, "
+                     "Adam, AdamW, Adagrad or RMSprop on GPU tensors), or clip before step() yourself")
 _NEEDS_SGD = "fused=True needs a single-group, dampening-free torch.optim.SGD on GPU tensors"
 
 
@@ -358,8 +360,11 @@ class _DistributedOptimizer:
 
     def __init__(self, optimizer, named_parameters=None, compression=Compression.none,
                  backward_passes_per_step: int = 1, op=Average, bucket_mb: float = DEFAULT_BUCKET_MB,
-                 gradient_predivide_factor: float = 1.0, fused: Optional[bool] = None):
+                 gradient_predivide_factor: float = 1.0, fused: Optional[bool] = None,
+                 clip_norm: Optional[float] = None):
         _need_init()
+        if clip_norm is not None and fused is False:
+            raise ValueError(_CLIP_NEEDS_FUSED)
         if op not in (Average, Sum):
             raise ValueError("DistributedOptimizer supports op=Average or op=Sum")
         self.optimizer = optimizer
@@ -402,23 +407,29 @@ class _DistributedOptimizer:
         self._kind = "sgd"
         if fused is None:
             fused = can_fuse
+            if clip_norm is not None and not fused:
+                raise ValueError(_CLIP_NEEDS_FUSED)
         elif fused and not can_fuse:
             if not isinstance(optimizer, (torch.optim.Adam, torch.optim.AdamW, torch.optim.Adagrad,
                                           torch.optim.RMSprop)):
                 raise ValueError(_NEEDS_SGD)
             self._kind = _fused_family(optimizer, self.groups)
+        # clip_norm (fused only): the global norm of the averaged gradient over ALL dtype groups -- one partial
+        # block per group, folded together on the device (ops/optim.py), then each group's clipped apply
+        self._clip = clip_norm is not None
+        xkw = {"clip_norm": clip_norm} if self._clip else {}
         if fused and self._kind != "sgd":
             from ..ops.optim import FlatAdagrad, FlatAdam, FlatRMSProp
 
             g = optimizer.param_groups[0]
             for flat, _ in self.groups:
                 if self._kind == "adam":
-                    fo = FlatAdam(flat.data, float(g["lr"]))
+                    fo = FlatAdam(flat.data, float(g["lr"]), **xkw)
                 elif self._kind == "adagrad":
                     fo = FlatAdagrad(flat.data, float(g["lr"]),
-                                     initial_accumulator_value=g.get("initial_accumulator_value", 0.0))
+                                     initial_accumulator_value=g.get("initial_accumulator_value", 0.0), **xkw)
                 else:
-                    fo = FlatRMSProp(flat.data, float(g["lr"]))
+                    fo = FlatRMSProp(flat.data, float(g["lr"]), **xkw)
                 self._fused.append((flat, fo))
             self._sync_hp()
         elif fused:
@@ -431,7 +442,10 @@ class _DistributedOptimizer:
                 master = flat.data if flat.data.dtype == torch.float32 else flat.data.float().clone()
                 self._fused.append((flat, FlatSGD(master, g["lr"], momentum=g["momentum"],
                                                   weight_decay=g["weight_decay"], nesterov=g["nesterov"],
-                                                  resync=master is not flat.data)))
+                                                  resync=master is not flat.data, **xkw)))
+        if fused and self._clip:
+            for _, opt in self._fused[1:]:
+                opt.share_partials(self._fused[0][1], len(self._fused))
         if fused:
             # torch state index of every parameter -> (flat buffer, slot)
             slot_of = {}
@@ -560,16 +574,21 @@ class _DistributedOptimizer:
         loss = closure() if closure is not None else None
         if self._kind != "sgd":
             self._sync_hp()
-            for flat, opt in self._fused:
-                opt.step(flat.grad)  # fp32: the flat buffer is the master, updated in place
-            return loss
-        g = self.optimizer.param_groups[0]  # lr schedules edit the wrapped optimizer's group
+        else:
+            g = self.optimizer.param_groups[0]  # lr schedules edit the wrapped optimizer's group
+            for _, opt in self._fused:
+                opt.lr, opt.momentum, opt.weight_decay = g["lr"], g["momentum"], g["weight_decay"]
+        if self._clip:  # every group's sum of squares first: one norm over all of them
+            for i, (flat, opt) in enumerate(self._fused):
+                opt.begin_step()
+                opt.accumulate_sumsq(flat.grad, i)
+            for _, opt in self._fused:
+                opt.finish_norm(len(self._fused))
         for flat, opt in self._fused:
-            opt.lr, opt.momentum, opt.weight_decay = g["lr"], g["momentum"], g["weight_decay"]
-            if opt.w is flat.data:
-                opt.step(flat.grad)  # fp32: updated in place
-            else:
-                opt.step(flat.grad, out_bf16=flat.data)
+            if not self._clip:
+                opt.begin_step()
+            # an fp32 flat buffer is the master, updated in place; a bf16 one is the compute copy of SGD's master
+            opt.apply_range(flat.grad, 0, None if opt.w is flat.data else flat.data)
         return loss
 
     def __getattr__(self, name):
@@ -580,7 +599,8 @@ def DistributedOptimizer(optimizer, named_parameters=None, compression=Compressi
                          backward_passes_per_step: int = 1, op=Average, **kw):
     """Horovod's DistributedOptimizer: bucketed gradient averaging overlapped with backward; a plain
     torch SGD on GPU tensors is applied by the fused HIP kernel (``fused=False`` keeps torch's); ``fused=True``
-    also takes a single-group Adam / AdamW / Adagrad / RMSprop over fp32 GPU parameters."""
+    also takes a single-group Adam / AdamW / Adagrad / RMSprop over fp32 GPU parameters.  ``clip_norm`` (fused
+    only) clips the averaged gradient by its global norm over all parameters before the apply."""
     return _DistributedOptimizer(optimizer, named_parameters, compression, backward_passes_per_step, op, **kw)
 
 

@@ -41,9 +41,24 @@ Only the last bucket (the stem's gradients) is exposed after backward.
 Gradients are averaged over workers (TF SyncReplicasOptimizer semantics) by the optimizer's
 ``grad_scale``.  ``wire_dtype=torch.float32`` pushes and sums fp32 gradients (the reference TF job
 is fp32 end to end) even when the gradient buffer the kernels accumulate into is bf16.
+
+Clipping, non-finite skip and EMA (``clip_norm`` / ``skip_nonfinite`` / ``ema_decay`` / ``ema_warmup``, the rest of
+the Inception-v3 recipe beside ``rmsprop_tf``; ops/optim.py).  The EMA alone changes nothing in the flow above: each
+apply also updates the owner's fp32 EMA shard.  A global norm does: it is the norm of the WHOLE averaged gradient,
+which no rank has before the last bucket is pushed.  Each bucket is still pushed as soon as its gradients are
+complete, and its owner then reduces the piece it received to per-workgroup sums of squares (one partial block per
+bucket, a fixed order, so the same bits every time); apply and pull of every bucket wait for the end of backward,
+where the partial blocks are summed over the ranks (one small all-reduce), folded into one coefficient on the
+device and the buckets applied and pulled in bucket order.  Every rank sums the same blocks in the same order, so
+all compute the identical coefficient.  Clipping therefore trades the overlap of apply and pull with backward for
+the global norm (the pushes still overlap).  The xGMI data plane applies chunk by chunk as rows land, before any
+norm can exist: it refuses these options (use ``plane="rccl"``).
+
+``ema_weights()`` swaps the EMA into the variables for an evaluation and restores them afterwards.
 """
 from __future__ import annotations
 
+import contextlib
 import math
 import os
 import time
@@ -52,10 +67,13 @@ from typing import Dict, List, Optional
 import torch
 import torch.distributed as dist
 
-from ..ops.optim import FlatAdagrad, FlatAdam, FlatRMSProp, FlatSGD
+from ..ops.optim import SUMSQ_BLOCKS, FlatAdagrad, FlatAdam, FlatRMSProp, FlatSGD
 from . import collectives as coll
 from .buckets import DEFAULT_BUCKET_MB, Bucket, GradBucketEngine, make_buckets
 from .flat import FlatParams
+
+
+_EXTRAS = ("clip_norm", "skip_nonfinite", "ema_decay", "ema_warmup")
 
 
 def make_optimizer(kind: str, master: torch.Tensor, lr: float, momentum: float = 0.9, weight_decay: float = 0.0,
@@ -66,19 +84,23 @@ def make_optimizer(kind: str, master: torch.Tensor, lr: float, momentum: float =
     ``eps`` defaults to 1.0, the Inception recipe's value (RMSProp decay 0.9, momentum 0.9, epsilon 1.0), so that
     ``bench.py --optimizer rmsprop_tf``, which passes no ``eps``, trains with that recipe."""
     kind = kind.lower()
+    # clip_norm / skip_nonfinite / ema_decay / ema_warmup: every kind takes them (ops/optim.py _FlatOptimizer)
+    extra = {k: kw[k] for k in _EXTRAS if k in kw}
     if kind in ("sgd", "momentum"):
-        return FlatSGD(master, lr, momentum=momentum, weight_decay=weight_decay, nesterov=kw.get("nesterov", False))
+        return FlatSGD(master, lr, momentum=momentum, weight_decay=weight_decay, nesterov=kw.get("nesterov", False),
+                       **extra)
     if kind in ("adam", "adamw"):
         return FlatAdam(master, lr, betas=kw.get("betas", (0.9, 0.999)), eps=kw.get("eps", 1e-8),
-                        weight_decay=weight_decay, decoupled=(kind == "adamw"))
+                        weight_decay=weight_decay, decoupled=(kind == "adamw"), **extra)
     if kind == "adagrad":
         return FlatAdagrad(master, lr, eps=kw.get("eps", 1e-7),
                            initial_accumulator_value=kw.get("initial_accumulator_value", 0.1),
-                           weight_decay=weight_decay)
+                           weight_decay=weight_decay, **extra)
     if kind in ("rmsprop", "rmsprop_tf"):
         tf_style = kind == "rmsprop_tf"
         return FlatRMSProp(master, lr, alpha=kw.get("alpha", 0.9), momentum=momentum,
-                           eps=kw.get("eps", 1.0 if tf_style else 1e-8), weight_decay=weight_decay, tf_style=tf_style)
+                           eps=kw.get("eps", 1.0 if tf_style else 1e-8), weight_decay=weight_decay, tf_style=tf_style,
+                           **extra)
     raise ValueError(f"unknown optimizer {kind!r}")
 
 
@@ -95,7 +117,14 @@ class ParameterServer:
                  weight_decay: float = 0.0, mode: str = "colocated", sync: bool = True, ps_ranks=(0,),
                  group=None, dtype=torch.bfloat16, device=None, wire_dtype: Optional[torch.dtype] = None,
                  bucket_mb: float = DEFAULT_BUCKET_MB, bucketed_single: bool = False, plane: str = "auto",
-                 **opt_kw):
+                 clip_norm: Optional[float] = None, skip_nonfinite: bool = False, ema_decay: Optional[float] = None,
+                 ema_warmup: bool = False, **opt_kw):
+        self.needs_norm = clip_norm is not None or bool(skip_nonfinite)
+        self.has_ema = ema_decay is not None
+        if self.needs_norm or self.has_ema:
+            opt_kw.update(clip_norm=clip_norm, skip_nonfinite=skip_nonfinite, ema_decay=ema_decay,
+                          ema_warmup=ema_warmup)
+            self._refuse_plane_extras(model, mode, plane, device, group)  # before any tensor is made
         self.mode = mode
         self.sync = sync
         self.group = group
@@ -193,6 +222,15 @@ class ParameterServer:
                 self.plane_kind = "rccl"
                 for opt in self.optimizers.values():
                     opt.grad_scale = 1.0 / len(self.worker_ranks) if sync else 1.0
+        # a global norm: one partial block per bucket, applies and pulls deferred to the end of backward
+        self._norm_deferred = self.needs_norm and self.plane is None
+        self._foreign_blocks = None
+        if self._norm_deferred:
+            for opt in self.optimizers.values():
+                opt.partials(len(self.buckets))
+            foreign = [b.index for b in self.buckets if self._master_range[b.index] is None]
+            if foreign and self.optimizers:
+                self._foreign_blocks = torch.tensor(foreign, dtype=torch.long, device=f.device)
         self._wire = None
         if self.world > 1 and self.wire_dtype != f.grad.dtype and self.plane is None:
             self._wire = torch.zeros(f.numel, dtype=self.wire_dtype, device=f.device)
@@ -206,6 +244,19 @@ class ParameterServer:
             self.engine.attach()
 
     # -- helpers ---------------------------------------------------------------
+    @staticmethod
+    def _refuse_plane_extras(model, mode, plane, device, group):
+        """clip_norm / skip_nonfinite / ema_decay on the xGMI data plane: refused before the plane (or any
+        tensor) is built.  An explicit ``plane="xgmi"`` is refused whatever the topology resolves it to."""
+        want = plane
+        if plane == "auto" and mode == "dedicated" and coll.world(group) > 1:
+            dev = torch.device(device) if device is not None else next(model.parameters()).device
+            want = os.environ.get("TONY_PS_PLANE", "xgmi") if dev.type == "cuda" else "rccl"
+        if want == "xgmi":
+            raise ValueError("clip_norm, skip_nonfinite and ema_decay are not available on the xGMI PS data plane: "
+                             "it applies chunk by chunk as the workers' rows land, before a global norm exists, and "
+                             "keeps no EMA; construct the ParameterServer with plane=\"rccl\"")
+
     def zero_grad(self):
         self.flat.zero_grad()
 
@@ -255,12 +306,15 @@ class ParameterServer:
                 self.begin_step()
             self._begun = False
             opt = self.optimizers[self.rank]
+            if self.needs_norm:  # begin_step pushed the hyper-parameters: norm, then the one fused apply
+                opt.accumulate_sumsq(self.flat.grad, 0)
+                opt.finish_norm(1)
             self._apply(opt, self.flat.grad, 0, self.flat.data)
             self.steps += 1
             return
         if not self.engine.armed:
             self.begin_step(overlap=False)
-        self.engine.end()
+        self.engine.end(finish=self._finish_norm if self._norm_deferred else None)
         self.steps += 1
 
     @property
@@ -312,11 +366,18 @@ class ParameterServer:
             m, p = self._master_range[b.index]
             own = f.data[b.lo + self.rank * p:b.lo + (self.rank + 1) * p]
             if self.world == 1:
+                if self._norm_deferred:
+                    opt.accumulate_sumsq(f.grad[b.lo:b.hi], b.index)
+                    return
                 self._apply(opt, f.grad[b.lo:b.hi], m, own)
                 return
             g = self._wire_grad(b)
             gs = self._gshard[m:m + p]
             _wait(coll.reduce_scatter_flat(gs, g, group=self.group, async_op=True))     # push
+            if self._norm_deferred:  # the piece's share of the global norm; apply + pull in _finish_norm
+                opt.accumulate_sumsq(gs, b.index)
+                self.push_bytes += g.numel() * g.element_size()
+                return
             self._apply(opt, gs, m, own)                                                  # apply (HIP)
             _wait(coll.all_gather_flat(f.data[b.lo:b.hi], own, group=self.group, async_op=True))  # pull
             self.push_bytes += g.numel() * g.element_size()
@@ -324,6 +385,12 @@ class ParameterServer:
         owner = self._owner(b)
         g = self._wire_grad(b)
         _wait(dist.reduce(g, dst=owner, group=self.group, async_op=True))                # push
+        if self._norm_deferred:
+            if self.rank == owner:
+                opt.accumulate_sumsq(g, b.index)
+            if self.is_worker:
+                self.push_bytes += g.numel() * g.element_size()
+            return
         if self.rank == owner:
             m, _ = self._master_range[b.index]
             self._apply(opt, g, m, f.data[b.lo:b.hi])                                     # apply
@@ -331,12 +398,57 @@ class ParameterServer:
         if self.is_worker:
             self.push_bytes += g.numel() * g.element_size()
 
+    def _finish_norm(self):
+        """End of backward with a global norm (the communication stream is current): every bucket is pushed and
+        its owner's partial block written.  Sum the blocks over the ranks, fold them into the coefficient, then
+        apply and pull every bucket in bucket order."""
+        f = self.flat
+        opt = self.optimizers.get(self.rank)
+        nb = len(self.buckets)
+        if len(self.ps_ranks) > 1:
+            # more than one rank holds pieces.  A block is zero on a rank that owns nothing of its bucket, and a
+            # rank without a shard (a dedicated worker) contributes zeros, so the sum is every piece's block once
+            part = opt.partials(nb) if opt is not None else torch.zeros(nb * SUMSQ_BLOCKS, dtype=torch.float32,
+                                                                        device=f.device)
+            _wait(coll.all_reduce(part, group=self.group, async_op=True))
+        if opt is not None:
+            opt.finish_norm(nb)
+            if self._foreign_blocks is not None:  # the other owners' blocks: zero again for the next step's sum
+                opt.partials(nb).view(nb, SUMSQ_BLOCKS).index_fill_(0, self._foreign_blocks, 0.0)
+        for b in self.buckets:
+            if self.mode == "colocated":
+                m, p = self._master_range[b.index]
+                own = f.data[b.lo + self.rank * p:b.lo + (self.rank + 1) * p]
+                if self.world == 1:
+                    self._apply(opt, f.grad[b.lo:b.hi], m, own)
+                    continue
+                self._apply(opt, self._gshard[m:m + p], m, own)                              # apply (HIP)
+                _wait(coll.all_gather_flat(f.data[b.lo:b.hi], own, group=self.group, async_op=True))  # pull
+                continue
+            owner = self._owner(b)
+            if self.rank == owner:
+                m, _ = self._master_range[b.index]
+                self._apply(opt, self._wire_grad_view(b), m, f.data[b.lo:b.hi])
+            _wait(dist.broadcast(f.data[b.lo:b.hi], src=owner, group=self.group, async_op=True))
+
+    def _wire_grad_view(self, b: Bucket) -> torch.Tensor:
+        """Where bucket b's reduced gradient sits after its push (no copy: ``_wire_grad`` already staged it)."""
+        return (self._wire if self._wire is not None else self.flat.grad)[b.lo:b.hi]
+
     def _apply(self, opt, grad: torch.Tensor, m: int, out: torch.Tensor):
         if out.dtype == torch.bfloat16 or not out.is_cuda:
             opt.apply_range(grad, m, out_bf16=out)
         else:  # fp32 variables (reference-precision runs): the master range IS the new value
             opt.apply_range(grad, m, out_bf16=None)
             out.copy_(opt.w[m:m + out.numel()])
+
+    def _step_whole(self, opt, grad: torch.Tensor):
+        """One whole-buffer update (the async ps applies each push on its own, norm included)."""
+        opt.begin_step()
+        if self.needs_norm:
+            opt.accumulate_sumsq(grad, 0)
+            opt.finish_norm(1)
+        self._apply(opt, grad, 0, self.flat.data)
 
     def _step_dedicated_async_worker(self):
         f = self.flat
@@ -359,8 +471,7 @@ class ParameterServer:
             buf = torch.empty_like(f.grad)
             for done in range(total_pushes):
                 w = dist.recv(buf, group=self.group)  # returns the sender's global rank
-                opt.begin_step()
-                self._apply(opt, buf, 0, f.data)
+                self._step_whole(opt, buf)
                 dist.send(f.data, dst=w, group=self.group)
             self.steps = total_pushes
             return
@@ -374,8 +485,7 @@ class ParameterServer:
                 if req is None or not req.is_completed():
                     continue
                 req.wait()
-                opt.begin_step()
-                self._apply(opt, bufs[w], 0, f.data)        # apply on arrival
+                self._step_whole(opt, bufs[w])              # apply on arrival
                 dist.send(f.data, dst=w, group=self.group)  # the worker's pull
                 done += 1
                 got[w] += 1
@@ -385,6 +495,49 @@ class ParameterServer:
             if not progressed:
                 time.sleep(poll_s)
         self.steps = done
+
+    # -- evaluation on the EMA of the variables ----------------------------------
+    def _distribute(self, source):
+        """Write ``source(opt)`` (the fp32 masters or their EMA, in master-shard order) into the variables by the
+        route a pull takes: each owner casts its pieces, an all-gather / broadcast hands them to every rank."""
+        f = self.flat
+        opt = self.optimizers.get(self.rank)
+        with torch.no_grad():
+            if self.mode == "dedicated" and not self.sync:  # the one ps task owns the buffer in flat order
+                if opt is not None:
+                    f.data.copy_(source(opt))
+                coll.broadcast(f.data, src=self.ps_ranks[0], group=self.group)
+                return
+            for b in self.buckets:
+                if self.mode == "colocated":
+                    m, p = self._master_range[b.index]
+                    own = f.data[b.lo + self.rank * p:b.lo + (self.rank + 1) * p]
+                    own.copy_(source(opt)[m:m + p])
+                    _wait(coll.all_gather_flat(f.data[b.lo:b.hi], own, group=self.group, async_op=True))
+                    continue
+                owner = self._owner(b)
+                if self.rank == owner:
+                    m, n = self._master_range[b.index]
+                    f.data[b.lo:b.hi].copy_(source(opt)[m:m + n])
+                _wait(coll.broadcast(f.data[b.lo:b.hi], src=owner, group=self.group, async_op=True))
+
+    @contextlib.contextmanager
+    def ema_weights(self):
+        """Evaluate on the exponential moving average of the variables (``ema_decay``): inside the block the
+        model's parameters hold the EMA (each shard owner casts its piece, the pull's all-gather / broadcast
+        distributes it), on exit they are restored from the fp32 masters by the same route, bit for bit what
+        the last step wrote.  Collective: every rank enters and leaves together, between steps.
+
+        Weight caches derived from the parameters (a ``Trainer``'s transposed dgrad weights) do not follow by
+        themselves: the caller refreshes them after entering and after leaving, as a step does, with the
+        Trainer's ``wt.refresh()``."""
+        if not self.has_ema:
+            raise RuntimeError("ema_weights() needs a ParameterServer built with ema_decay")
+        self._distribute(lambda opt: opt.ema)
+        try:
+            yield self
+        finally:
+            self._distribute(lambda opt: opt.w)
 
     # -- checkpoint ------------------------------------------------------------
     def layout(self) -> dict:

@@ -36,7 +36,8 @@ def classify(name):
         return "tony HIP: in-place grad accumulate"
     if "box3_kernel" in n or "maxpool_" in n or "avgpool_" in n:
         return "tony HIP: pooling"
-    if "sgd_kernel" in n or "adam_kernel" in n or "grad_stats" in n:
+    if "sgd_kernel" in n or "adam_kernel" in n or "grad_stats" in n or "grad_sumsq_kernel" in n \
+            or "clip_ctl_kernel" in n or "apply_x_kernel" in n:
         return "tony HIP: fused optimizer"
     if "xent" in n:
         return "tony HIP: fused xent"
