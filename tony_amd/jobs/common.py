@@ -57,5 +57,25 @@ def synthetic_images(n: int, res: int, classes: int, device, dtype=torch.bfloat1
     return x, y
 
 
+def evaluate(model, eval_dir: str, batch: int, size: int, kind: str, device, dtype, rank: int, world: int):
+    """Top-1 / top-5 counters ``[hit@1, hit@5, images]`` (int64, on ``device``) of ``model`` in eval mode over
+    this rank's share of the shards in ``eval_dir`` (central crop, file order); the caller all-reduces them."""
+    from tony_amd.data.images import ImageBatches
+    from tony_amd.ops.metrics import TopK
+
+    top = TopK(5, device)
+    was_training = model.training
+    model.eval()
+    try:
+        with ImageBatches(eval_dir, batch, size, train=False, model=kind, device=device, dtype=dtype, rank=rank,
+                          world=world) as batches, torch.no_grad():
+            for x, y in batches:
+                out = model(x)
+                top.update(out[0] if isinstance(out, tuple) else out, y)
+    finally:
+        model.train(was_training)
+    return top.counters
+
+
 def exit_code(ok: bool) -> None:
     sys.exit(0 if ok else 1)

@@ -43,7 +43,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspa
 import torch  # noqa: E402
 import torch.distributed as dist  # noqa: E402
 
-from tony_amd.jobs.common import Throughput, log, metric, synthetic_images, working_dir  # noqa: E402
+from tony_amd.jobs.common import Throughput, evaluate, log, metric, synthetic_images, working_dir  # noqa: E402
 from tony_amd.parallel import bootstrap  # noqa: E402
 from tony_amd.parallel.ps import ParameterServer  # noqa: E402
 from tony_amd.parallel.tf_config import TFConfig  # noqa: E402
@@ -77,6 +77,12 @@ def main(argv=None) -> int:
     ap.add_argument("--ema-decay", type=float, default=0.0,
                     help="keep an exponential moving average of the variables on the ps and report the loss of one "
                          "forward on it at the end (0: off; the published recipe uses 0.9999)")
+    ap.add_argument("--data-dir", default=None,
+                    help="train from the uint8 shards in DIR (tony_amd/data/images.py: random crop, flip, resize on "
+                         "the GPU) instead of one synthetic batch")
+    ap.add_argument("--eval-dir", default=None,
+                    help="after training, top-1 / top-5 over the shards in DIR (central crop, eval mode, the EMA "
+                         "weights when --ema-decay is set)")
     a = ap.parse_args(argv)
     tc = TFConfig.from_env()
     on_gpu = torch.cuda.is_available()
@@ -176,10 +182,15 @@ def main(argv=None) -> int:
         if ps.has_ema:
             with ps.ema_weights():  # collective: the ps task hands its EMA shard to the workers' evaluation
                 pass
+        if a.eval_dir and ps.has_ema:
+            with ps.ema_weights():  # ... and once more to the workers' top-k evaluation
+                pass
         if on_gpu:
             torch.cuda.synchronize()
         if ps.plane is not None:
             ps.plane.check_error()
+        if a.eval_dir:  # the workers' [hit@1, hit@5, images] sum (the ps adds none)
+            dist.all_reduce(torch.zeros(3, dtype=torch.int64, device=dev if on_gpu else "cpu"))
         rate = torch.zeros(1, dtype=torch.float64, device=dev if on_gpu else "cpu")
         dist.all_reduce(rate)  # the workers' images/sec sum (the ps adds none)
         dist.barrier()
@@ -189,7 +200,18 @@ def main(argv=None) -> int:
         return 0
 
     trainer = Trainer(model, ps, loss_fn, use_graph=on_gpu and a.graph)
-    x, y = synthetic_images(a.batch_size, a.image_size, 1000, dev, dtype, seed=rank)
+    # the workers' share of the data: the ps task of a dedicated PS reads none
+    data_rank, data_world = ps.worker_ranks.index(rank), len(ps.worker_ranks)
+    batches = None
+    if a.data_dir:
+        from tony_amd.data.images import ImageBatches
+
+        batches = ImageBatches(a.data_dir, a.batch_size, a.image_size, train=True, model="inception", device=dev,
+                               dtype=dtype, seed=0, rank=data_rank, world=data_world)
+        batches.seek(start)  # batch t is a pure function of t: a resumed gang continues where it was
+        wait0 = 0.0
+    else:
+        x, y = synthetic_images(a.batch_size, a.image_size, 1000, dev, dtype, seed=rank)
     tp = Throughput(dev)
     timed = 0
     loss = torch.zeros(())
@@ -209,6 +231,10 @@ def main(argv=None) -> int:
         if s == timed_from:
             dist.barrier()
             tp.start()
+            if batches is not None:
+                wait0 = batches.wait_ms
+        if batches is not None:
+            x, y = batches.next()
         loss = trainer.step(x, y)
         if s >= max(start, a.warmup):
             tp.add(a.batch_size)
@@ -227,7 +253,24 @@ def main(argv=None) -> int:
         model.train()
         log(f"loss on the EMA weights (decay {a.ema_decay}): {ema_loss:.4f} (last training loss {float(loss):.4f})")
     rate = torch.tensor([tp.rate() if timed else 0.0], dtype=torch.float64, device=dev if on_gpu else "cpu")
-    dist.all_reduce(rate)
+    extra = {}
+    if batches is not None:
+        extra["input_wait_ms_per_step"] = (batches.wait_ms - wait0) / max(timed, 1)
+        log(f"input: {extra['input_wait_ms_per_step']:.3f} ms per step blocked on the filler, "
+            f"{batches.fill_ms / max(batches.filled, 1):.2f} ms to fill a batch, "
+            f"{batches.backpressure_ms:.0f} ms in all waiting for the GPU to take a slot")
+        batches.close()
+    if a.eval_dir:
+        import contextlib
+
+        with ps.ema_weights() if ps.has_ema else contextlib.nullcontext():
+            counts = evaluate(model, a.eval_dir, a.batch_size, a.image_size, "inception", dev, dtype, data_rank,
+                              data_world)
+        dist.all_reduce(counts)
+        hit1, hit5, seen = (int(v) for v in counts.tolist())
+        extra.update(top1=hit1 / max(seen, 1), top5=hit5 / max(seen, 1), eval_images=seen)
+        log(f"evaluation over {seen} images: top-1 {extra['top1']:.4f}, top-5 {extra['top5']:.4f}")
+    dist.all_reduce(rate)  # (taken before the evaluation, which is not training throughput)
     workers = len(ps.worker_ranks)
     if tc.is_chief or rank == 0:
         from tony_amd.parallel import collectives as coll
@@ -237,7 +280,7 @@ def main(argv=None) -> int:
         metric(model="inception_v3", images_per_sec=float(rate), workers=workers, ps_mode=mode, loss=float(loss),
                dtype="fp32" if dtype == torch.float32 else "bf16", x3=x3, sync=ps.sync,
                start_step=start, steps=total, plane=_plane_name(ps), verified=coll.data_plane_status(),
-               collective_fallbacks=coll.fallback_count())
+               collective_fallbacks=coll.fallback_count(), **extra)
     log(f"{float(rate):.1f} images/sec total over {workers} workers ({mode} PS)")
     dist.barrier()
     # orderly shutdown: drain the device (side streams included) and tear the process group down before

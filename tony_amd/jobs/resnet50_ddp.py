@@ -22,7 +22,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspa
 
 import torch  # noqa: E402
 
-from tony_amd.jobs.common import Throughput, log, metric, synthetic_images  # noqa: E402
+from tony_amd.jobs.common import Throughput, evaluate, log, metric, synthetic_images  # noqa: E402
 from tony_amd.models.layers import cast_model  # noqa: E402
 from tony_amd.models.resnet import resnet50  # noqa: E402
 from tony_amd.parallel import bootstrap  # noqa: E402
@@ -37,6 +37,10 @@ def main(argv=None) -> int:
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--image-size", type=int, default=224)
     ap.add_argument("--bucket-mb", type=float, default=32)
+    ap.add_argument("--data-dir", default=None,
+                    help="train from the uint8 shards in DIR (tony_amd/data/images.py) instead of one synthetic batch")
+    ap.add_argument("--eval-dir", default=None,
+                    help="after training, top-1 / top-5 over the shards in DIR (central crop, eval mode)")
     a = ap.parse_args(argv)
     rank, world, _, dev = bootstrap.init_from_env()
     on_gpu = dev.type == "cuda"
@@ -46,7 +50,15 @@ def main(argv=None) -> int:
     model = cast_model(resnet50(fused=on_gpu), dtype, dev).to(memory_format=torch.channels_last)
     ddp = DistributedDataParallel(model, bucket_mb=a.bucket_mb)
     opt = torch.optim.SGD(model.parameters(), lr=0.1 * world, momentum=0.9, weight_decay=5e-5)
-    x, y = synthetic_images(a.batch_size, a.image_size, 1000, dev, dtype, seed=rank)
+    batches = None
+    if a.data_dir:
+        from tony_amd.data.images import ImageBatches
+
+        batches = ImageBatches(a.data_dir, a.batch_size, a.image_size, train=True, model="resnet", device=dev,
+                               dtype=dtype, seed=0, rank=rank, world=world)
+        wait0 = 0.0
+    else:
+        x, y = synthetic_images(a.batch_size, a.image_size, 1000, dev, dtype, seed=rank)
     tp = Throughput(dev)
     loss = None
     for s in range(a.warmup + a.steps):
@@ -54,6 +66,10 @@ def main(argv=None) -> int:
             if world > 1:
                 torch.distributed.barrier()
             tp.start()
+            if batches is not None:
+                wait0 = batches.wait_ms
+        if batches is not None:
+            x, y = batches.next()
         ddp.zero_grad()
         loss = torch.nn.functional.cross_entropy(ddp(x).float(), y)
         loss.backward()
@@ -65,8 +81,23 @@ def main(argv=None) -> int:
         t = torch.tensor([rate], dtype=torch.float64, device=dev)
         coll.all_reduce(t)
         rate = float(t.item())
+    extra = {}
+    if batches is not None:
+        extra["input_wait_ms_per_step"] = (batches.wait_ms - wait0) / max(a.steps, 1)
+        log(f"input: {extra['input_wait_ms_per_step']:.3f} ms per step blocked on the filler, "
+            f"{batches.fill_ms / max(batches.filled, 1):.2f} ms to fill a batch, "
+            f"{batches.backpressure_ms:.0f} ms in all waiting for the GPU to take a slot")
+        batches.close()
+    if a.eval_dir:
+        counts = evaluate(model, a.eval_dir, a.batch_size, a.image_size, "resnet", dev, dtype, rank, world)
+        if world > 1:
+            torch.distributed.all_reduce(counts)
+        hit1, hit5, seen = (int(v) for v in counts.tolist())
+        extra.update(top1=hit1 / max(seen, 1), top5=hit5 / max(seen, 1), eval_images=seen)
+        log(f"evaluation over {seen} images: top-1 {extra['top1']:.4f}, top-5 {extra['top5']:.4f}")
     if rank == 0:
-        metric(model="resnet50", images_per_sec=rate, world=world, batch_per_rank=a.batch_size, loss=float(loss))
+        metric(model="resnet50", images_per_sec=rate, world=world, batch_per_rank=a.batch_size, loss=float(loss),
+               **extra)
     log(f"{rate:.1f} images/sec over {world} ranks")
     if world > 1:
         torch.distributed.destroy_process_group()

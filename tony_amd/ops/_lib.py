@@ -99,6 +99,10 @@ _SIGNATURES = {
     "tony_xent_fwd": [c_void_p, c_int, c_int64, c_int, c_int64, c_void_p, c_float, c_void_p, c_void_p, c_void_p],
     "tony_xent_bwd": [c_void_p, c_int, c_int64, c_int, c_int64, c_void_p, c_float, c_void_p, c_void_p, c_void_p,
                       c_int64, c_void_p],
+    # image input pipeline (csrc/image.hip, ops/image.py) and top-k evaluation counters (csrc/metrics.hip)
+    "tony_image_preprocess": [c_void_p, c_int, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_float,
+                              c_float, c_float, c_float, c_float, c_float, c_void_p],
+    "tony_topk_count": [c_void_p, c_int, c_int64, c_int, c_int64, c_void_p, c_int, c_void_p, c_void_p],
     "tony_dropout_fwd": [c_void_p, c_void_p, c_void_p, c_int64, c_int, c_float, c_void_p, c_void_p],
     "tony_dropout_bwd": [c_void_p, c_void_p, c_void_p, c_int64, c_int, c_float, c_void_p],
     "tony_counter_bump": [c_void_p, c_void_p],
