@@ -79,3 +79,17 @@ def evaluate(model, eval_dir: str, batch: int, size: int, kind: str, device, dty
 
 def exit_code(ok: bool) -> None:
     sys.exit(0 if ok else 1)
+
+
+def poly_warmup_lr(step: int, base_lr: float, warmup_steps: int, total_steps: int, power: float = 2.0,
+                   end_lr: float = 0.0) -> float:
+    """The LARS schedule: a linear warm-up to ``base_lr`` over ``warmup_steps`` steps (step 0 gets
+    ``base_lr / warmup_steps``), then polynomial decay to ``end_lr`` at ``total_steps``, where it stays."""
+    if warmup_steps < 0 or total_steps < warmup_steps:
+        raise ValueError(f"need 0 <= warmup_steps <= total_steps, got {warmup_steps} and {total_steps}")
+    if step < warmup_steps:
+        return base_lr * (step + 1) / warmup_steps
+    if step >= total_steps:
+        return end_lr
+    left = 1.0 - (step - warmup_steps) / (total_steps - warmup_steps)
+    return end_lr + (base_lr - end_lr) * left ** power

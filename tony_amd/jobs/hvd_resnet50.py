@@ -20,7 +20,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspa
 import torch  # noqa: E402
 
 import tony_amd.hvd as hvd  # noqa: E402
-from tony_amd.jobs.common import Throughput, log, metric, synthetic_images  # noqa: E402
+from tony_amd.jobs.common import Throughput, log, metric, poly_warmup_lr, synthetic_images  # noqa: E402
 from tony_amd.models.layers import cast_model  # noqa: E402
 from tony_amd.models.resnet import resnet50  # noqa: E402
 
@@ -32,6 +32,14 @@ def main(argv=None) -> int:
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--image-size", type=int, default=224)
     ap.add_argument("--bucket-mb", type=float, default=32)
+    ap.add_argument("--optimizer", default="sgd", choices=["sgd", "lars"],
+                    help="sgd (default): momentum SGD at a constant rate; lars: the same with per-tensor trust "
+                         "ratios (the large-batch recipe; BatchNorm parameters and biases are not adapted)")
+    ap.add_argument("--trust-coef", type=float, default=0.001, help="LARS trust coefficient")
+    ap.add_argument("--warmup-steps", type=int, default=0,
+                    help="lars: linear learning-rate warm-up over this many steps (0 with --decay-steps 0: constant)")
+    ap.add_argument("--decay-steps", type=int, default=0,
+                    help="lars: polynomial (power 2) decay to 0 at this step, counted from step 0")
     a = ap.parse_args(argv)
     hvd.init()
     dev = hvd.device()
@@ -41,13 +49,19 @@ def main(argv=None) -> int:
         torch.backends.cudnn.benchmark = True
     model = cast_model(resnet50(fused=on_gpu), dtype, dev).to(memory_format=torch.channels_last)
     opt = torch.optim.SGD(model.parameters(), lr=0.1 * hvd.size(), momentum=0.9, weight_decay=5e-5)
-    opt = hvd.DistributedOptimizer(opt, named_parameters=model.named_parameters(), bucket_mb=a.bucket_mb)
+    base_lr = 0.1 * hvd.size()
+    lars_kw = dict(fused=True, lars_coef=a.trust_coef) if a.optimizer == "lars" else {}
+    opt = hvd.DistributedOptimizer(opt, named_parameters=model.named_parameters(), bucket_mb=a.bucket_mb, **lars_kw)
+    scheduled = a.optimizer == "lars" and (a.warmup_steps > 0 or a.decay_steps > 0)
     x, y = synthetic_images(a.batch_size, a.image_size, 1000, dev, dtype, seed=hvd.rank())
     tp = Throughput(dev)
     for s in range(a.warmup + a.steps):
         if s == a.warmup:
             hvd.barrier()
             tp.start()
+        if scheduled:  # the host sets the rate; the fused optimizer's hyper-parameter push carries it to the device
+            opt.param_groups[0]["lr"] = poly_warmup_lr(s, base_lr, a.warmup_steps,
+                                                       a.decay_steps or a.warmup + a.steps)
         opt.zero_grad()
         loss = torch.nn.functional.cross_entropy(model(x).float(), y)
         loss.backward()
@@ -56,8 +70,9 @@ def main(argv=None) -> int:
             tp.add(a.batch_size)
     rate = float(hvd.allreduce(torch.tensor([tp.rate()]), op=hvd.Sum))
     if hvd.rank() == 0:
+        extra = dict(optimizer="lars", lr=opt.param_groups[0]["lr"]) if a.optimizer == "lars" else {}
         metric(model="resnet50", images_per_sec=rate, size=hvd.size(), batch_per_rank=a.batch_size,
-               loss=float(loss))
+               loss=float(loss), **extra)
     log(f"{rate:.1f} images/sec over {hvd.size()} ranks")
     hvd.shutdown()
     return 0

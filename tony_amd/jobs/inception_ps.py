@@ -69,9 +69,10 @@ def main(argv=None) -> int:
                     help="compute precision on GPU: bf16 (default) or fp32 -- the reference job's precision "
                          "(mnist_distributed.py: fp32 variables and compute): fp32 activations, variables and "
                          "pushed gradients, each conv / GEMM product as an x3 split over the bf16 MFMA kernels")
-    ap.add_argument("--optimizer", default="sgd", choices=["sgd", "rmsprop_tf"],
+    ap.add_argument("--optimizer", default="sgd", choices=["sgd", "rmsprop_tf", "lars", "lamb"],
                     help="sgd (default): momentum SGD; rmsprop_tf: the model's published recipe (RMSProp in TF's "
-                         "form, decay 0.9, momentum 0.9, epsilon 1.0)")
+                         "form, decay 0.9, momentum 0.9, epsilon 1.0); lars / lamb: momentum SGD / Adam with "
+                         "per-tensor trust ratios (BatchNorm parameters and biases are not adapted)")
     ap.add_argument("--clip-norm", type=float, default=0.0,
                     help="clip the averaged gradient by its global norm (0: off; the published recipe uses 2.0)")
     ap.add_argument("--ema-decay", type=float, default=0.0,
@@ -120,6 +121,10 @@ def main(argv=None) -> int:
                       ema_decay=a.ema_decay if a.ema_decay > 0 else None, plane="rccl")
         if mode == "dedicated" and on_gpu:
             log("--clip-norm / --ema-decay: the dedicated PS runs on the collective data plane (plane=rccl)")
+    if a.optimizer in ("lars", "lamb"):  # per-tensor norms need whole buckets before any apply: not the xGMI plane
+        extras["plane"] = "rccl"
+        if mode == "dedicated" and on_gpu:
+            log(f"--optimizer {a.optimizer}: the dedicated PS runs on the collective data plane (plane=rccl)")
     ps = ParameterServer(model, optimizer=a.optimizer, lr=0.045, momentum=0.9, weight_decay=4e-5, mode=mode,
                          ps_ranks=tc.ps_ranks if mode == "dedicated" else (0,), dtype=dtype, device=dev,
                          wire_dtype=torch.float32 if dtype == torch.float32 else None,

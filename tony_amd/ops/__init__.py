@@ -15,4 +15,5 @@ Hand-written HIP kernels (``csrc/*.hip``) built in-tree into
 from ._lib import KernelError, available, lib  # noqa: F401
 from .bn import BatchNormAct2d, bn_act  # noqa: F401
 from .loss import cross_entropy  # noqa: F401
-from .optim import FlatAdagrad, FlatAdam, FlatRMSProp, FlatSGD, grad_stats  # noqa: F401
+from .optim import (FlatAdagrad, FlatAdam, FlatLAMB, FlatLARS, FlatRMSProp, FlatSGD, Segments,  # noqa: F401
+                    grad_stats)

@@ -96,6 +96,17 @@ _SIGNATURES = {
     "tony_clip_ctl": [c_void_p, c_int, c_void_p, c_void_p, c_void_p],
     "tony_optim_apply_x": [c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_int64,
                            c_void_p, c_void_p, c_void_p, c_void_p],
+    # LARS / LAMB: per-tensor trust ratios over a work list of items (csrc/layerwise.hip)
+    "tony_layerwise_item_floats": [],
+    "tony_lars_norm": [c_void_p, c_void_p, c_int, c_void_p, c_int64, c_void_p, c_int, c_void_p, c_void_p, c_void_p],
+    "tony_lamb_norm": [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int64, c_void_p, c_int, c_void_p, c_void_p,
+                       c_void_p, c_void_p, c_void_p],
+    "tony_layerwise_fold": [c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p],
+    "tony_layerwise_ratio": [c_int, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p],
+    "tony_lars_apply": [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_int64, c_void_p, c_int, c_void_p,
+                        c_void_p, c_void_p, c_void_p, c_void_p],
+    "tony_lamb_apply": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_int, c_void_p,
+                        c_void_p, c_void_p, c_void_p, c_void_p],
     "tony_xent_fwd": [c_void_p, c_int, c_int64, c_int, c_int64, c_void_p, c_float, c_void_p, c_void_p, c_void_p],
     "tony_xent_bwd": [c_void_p, c_int, c_int64, c_int, c_int64, c_void_p, c_float, c_void_p, c_void_p, c_void_p,
                       c_int64, c_void_p],

@@ -68,7 +68,26 @@ __device__ __forceinline__ void rmsprop_update4(float* wf, float* sf, float* mf,
   }
 }
 
-// ema += (1 - d) (w - ema)   (tf.train.ExponentialMovingAverage.apply; omd = 1 - d, formed on the host in double)
+// LAMB (csrc/layerwise.hip).  The moments are Adam's with gk = g gs (gs carries the clip coefficient):
+//   m = b1 m + (1-b1) gk;  v = b2 v + (1-b2) gk^2
+__device__ __forceinline__ void lamb_moments4(float* mf, float* vf, const float* gf, float b1, float b2, float gs) {
+#pragma unroll
+  for (int k = 0; k < 4; ++k) {
+    const float gk = gf[k] * gs;
+    mf[k] = fmaf(b1, mf[k], (1.f - b1) * gk);
+    vf[k] = fmaf(b2, vf[k], (1.f - b2) * gk * gk);
+  }
+}
+
+// u = (m / bc1) / (sqrt(v / bc2) + eps) + wd_t w: the norm pass and the apply both form it with these very
+// operations from the stored m, v and the old w, so the norm is the norm of what is applied.
+__device__ __forceinline__ void lamb_u4(float* uf, const float* wf, const float* mf, const float* vf, float bc1,
+                                        float bc2, float eps, float wd) {
+#pragma unroll
+  for (int k = 0; k < 4; ++k) uf[k] = fmaf(wd, wf[k], (mf[k] / bc1) / (sqrtf(vf[k] / bc2) + eps));
+}
+
+// ema += (1 - d) (w - ema)  (tf.train.ExponentialMovingAverage.apply; omd = 1 - d, formed on the host in double)
 __device__ __forceinline__ void ema_update4(float* ef, const float* wf, float omd) {
 #pragma unroll
   for (int k = 0; k < 4; ++k) ef[k] = fmaf(omd, wf[k] - ef[k], ef[k]);

@@ -1,7 +1,7 @@
 """Fused optimizers over flat parameter shards (HIP kernels in csrc/optim.hip).
 
-``FlatSGD`` / ``FlatAdam`` / ``FlatAdagrad`` / ``FlatRMSProp`` own an fp32 master copy of a flat parameter
-shard plus its optimizer state, consume a flat gradient (bf16 or fp32) and write the
+``FlatSGD`` / ``FlatAdam`` / ``FlatAdagrad`` / ``FlatRMSProp`` / ``FlatLARS`` / ``FlatLAMB`` own an fp32 master
+copy of a flat parameter shard plus its optimizer state, consume a flat gradient (bf16 or fp32) and write the
 updated bf16 compute copy in the same pass.  The PS shard (``tony_amd.parallel.ps``)
 and the data-parallel engine use them directly; on CPU tensors the same update
 is computed with PyTorch ops (used by the CPU test-suite and local mode).
@@ -12,8 +12,15 @@ copy) before each step, so a captured HIP graph sees the current lr / step.
 Every kind also takes ``clip_norm`` (clipping by the global gradient norm), ``skip_nonfinite`` and ``ema_decay`` /
 ``ema_warmup`` (an EMA of the variables beside the master): see ``_FlatOptimizer``.  The norm, the clip
 coefficient and the skip decision stay on the device, so these too replay from a captured graph.
+
+``FlatLARS`` / ``FlatLAMB`` also take ``segments``, the table of where each parameter tensor lies in the shard, and
+scale every tensor's update by its own trust ratio (``_FlatLayerwise``, csrc/layerwise.hip).
 """
 from __future__ import annotations
+
+import bisect
+from dataclasses import dataclass
+from typing import List, Optional
 
 import torch
 
@@ -21,6 +28,7 @@ from . import _lib
 
 
 SUMSQ_BLOCKS = 1024  # floats of one partial block of tony_grad_sumsq (csrc/optim.hip kSumsqGrid; checked on use)
+ITEM_FLOATS = 4096   # longest work item of the layer-wise kernels (csrc/layerwise.hip kItemFloats; checked on use)
 N_XHP = 8            # xhp = [clip_norm, base_grad_scale, skip_nonfinite, ema_decay, 1 - ema_decay, 0, 0, 0]
 
 
@@ -502,6 +510,359 @@ class FlatRMSProp(_FlatOptimizer):
 
     def plane_state(self):
         return 3, self.ms, self.mom
+
+
+@dataclass
+class Segments:
+    """Where the parameter tensors lie in a master shard (built by ``parallel.flat.build_segments``).
+
+    ``starts``  K+1 ascending offsets in master coordinates, multiples of 4, from 0 to the shard's length;
+    ``tensor``  the global tensor id in [0, T) of each of the K segments (a tensor cut by a bucket or piece boundary
+                gives several segments, possibly on several ranks, with the same id);
+    ``adapt``   T booleans: tensor t takes a trust ratio and weight decay (else ratio 1, weight decay 0)."""
+
+    starts: List[int]
+    tensor: List[int]
+    adapt: List[bool]
+    names: Optional[List[str]] = None
+
+    @classmethod
+    def whole(cls, n: int) -> "Segments":
+        """The shard as one adapted tensor."""
+        return cls([0, int(n)], [0], [True])
+
+    def validate(self, n: int):
+        s = self.starts
+        if len(s) != len(self.tensor) + 1 or len(s) < 2 or s[0] != 0 or s[-1] != n:
+            raise ValueError(f"segments must cover [0, {n}) with one tensor id per segment")
+        if any(a % 4 for a in s) or any(b <= a for a, b in zip(s, s[1:])):
+            raise ValueError("segment offsets must be ascending multiples of 4")
+        if not self.adapt or any(not 0 <= t < len(self.adapt) for t in self.tensor):
+            raise ValueError(f"segment tensor ids must lie in [0, {len(self.adapt)})")
+
+
+class _FlatLayerwise(_FlatOptimizer):
+    """Common part of ``FlatLARS`` / ``FlatLAMB``: the update of every parameter tensor is scaled by a trust ratio
+    taken over that tensor alone (csrc/layerwise.hip).  A step is
+
+        ``norm_range``     once per bucket: a pair (sum w^2, sum x^2) per work item, a fixed order (LAMB's also
+                           updates the moments);
+        ``fold_norms``     once per step: ``tsum[T][2]``, each tensor's pairs summed in double -- a sharded caller
+                           all-reduces ``tsum`` here, so that a tensor cut over two ranks gets its whole norm;
+        ``finish_ratios``  once per step: the device table ``(ratio_t, wd_t)``;
+        ``apply_range``    once per bucket.
+
+    Ranges handed to ``norm_range`` / ``apply_range`` begin and end on segment boundaries or multiples of
+    ``ITEM_FLOATS`` inside a segment.  ``clip_norm`` / ``skip_nonfinite`` (``accumulate_sumsq`` + ``finish_norm``
+    come first, as for every kind) and the EMA compose: the clip coefficient multiplies the gradient before the
+    ratio is taken, a skipped step writes nothing."""
+
+    layer_kind = 0
+
+    def _init_segments(self, segments: Optional[Segments]):
+        n, dev = self.w.numel(), self.w.device
+        seg = segments if segments is not None else Segments.whole(n)
+        seg.validate(n)
+        self.segments = seg
+        T = len(seg.adapt)
+        if dev.type == "cuda" and _lib.lib().tony_layerwise_item_floats() != ITEM_FLOATS:
+            raise _lib.KernelError(f"{_lib.SO_PATH} is built for work items of "
+                                   f"{_lib.lib().tony_layerwise_item_floats()} floats, the Python side expects "
+                                   f"{ITEM_FLOATS}: rebuild")
+        items = []
+        for k, t in enumerate(seg.tensor):
+            lo, hi = seg.starts[k], seg.starts[k + 1]
+            items += [(a // 4, min(a + ITEM_FLOATS, hi) // 4, t, 0) for a in range(lo, hi, ITEM_FLOATS)]
+        self._item_lo = [4 * it[0] for it in items]
+        order = sorted(range(len(items)), key=lambda j: items[j][2])  # stable: a tensor's items in index order
+        tstart = [0] * (T + 1)
+        for it in items:
+            tstart[it[2] + 1] += 1
+        for t in range(T):
+            tstart[t + 1] += tstart[t]
+        i32 = dict(dtype=torch.int32, device=dev)
+        self._items = torch.tensor(items, **i32)
+        self._order = torch.tensor(order, **i32)
+        self._tstart = torch.tensor(tstart, **i32)
+        self._adapt = torch.tensor([int(bool(a)) for a in seg.adapt], **i32)
+        self._item_part = torch.zeros(len(items), 2, dtype=torch.float32, device=dev)
+        self._seg_part = torch.zeros(len(seg.tensor), 2, dtype=torch.float64)  # the CPU fallback's, per segment
+        self.tsum = torch.zeros(T, 2, dtype=torch.float32, device=dev)
+        self.table = torch.tensor([[1.0, 0.0]] * T, dtype=torch.float32, device=dev)
+
+    # -- ranges -------------------------------------------------------------------------------------------
+    def _check_range(self, grad, lo):
+        n = grad.numel()
+        if lo < 0 or lo + n > self.w.numel() or lo % 4 or n % 4:
+            raise ValueError(f"range [{lo}, {lo + n}) outside the {self.w.numel()}-element shard or not 4-aligned")
+        return n
+
+    def _item_range(self, lo: int, n: int):
+        """Work items [i0, i1) that make up master elements [lo, lo + n)."""
+        i0, i1 = bisect.bisect_left(self._item_lo, lo), bisect.bisect_left(self._item_lo, lo + n)
+        if n and (i0 >= len(self._item_lo) or self._item_lo[i0] != lo or
+                  (i1 < len(self._item_lo) and self._item_lo[i1] != lo + n)):
+            raise ValueError(f"range [{lo}, {lo + n}) does not begin and end on work-item boundaries: build the "
+                             "segments from the ranges that are applied")
+        return i0, i1
+
+    def _segs_in(self, lo: int, n: int):
+        """(k, a, b, tensor) of the segments that make up [lo, lo + n), for the CPU fallback."""
+        s = self.segments.starts
+        k0, k1 = bisect.bisect_left(s, lo), bisect.bisect_left(s, lo + n)
+        if n and (s[k0] != lo or s[k1] != lo + n):
+            raise ValueError(f"range [{lo}, {lo + n}) does not begin and end on segment boundaries")
+        return [(k, s[k], s[k + 1], self.segments.tensor[k]) for k in range(k0, k1)]
+
+    def _skipped_now(self) -> bool:
+        return self.needs_norm and self._ctl[1].item() != 0.0
+
+    def _coef_now(self) -> float:
+        return self._ctl[0].item() if self.needs_norm else 1.0
+
+    def _ctl_ptr(self) -> int:
+        return self._ctl.data_ptr() if self.needs_norm else 0
+
+    # -- the norm stages ----------------------------------------------------------------------------------
+    def norm_range(self, grad: torch.Tensor, lo: int = 0, out_bf16: torch.Tensor | None = None):
+        raise NotImplementedError
+
+    def fold_norms(self) -> torch.Tensor:
+        """``tsum[T][2]`` from the pairs of every ``norm_range`` of this step; returned for the cross-rank sum."""
+        if self.w.is_cuda:
+            rc = _lib.lib().tony_layerwise_fold(self._item_part.data_ptr(), self._order.data_ptr(),
+                                                self._tstart.data_ptr(), self.tsum.shape[0], self.tsum.data_ptr(),
+                                                _lib.stream_ptr(self.w.device))
+            _lib.check(rc, "tony_layerwise_fold")
+            return self.tsum
+        if self._skipped_now() and self.layer_kind == 1:
+            return self.tsum
+        acc = torch.zeros(self.tsum.shape, dtype=torch.float64)
+        acc.index_add_(0, torch.tensor(self.segments.tensor, dtype=torch.long), self._seg_part)
+        self.tsum.copy_(acc)
+        return self.tsum
+
+    def _ratio_cpu(self, sw: float, sx: float, coef: float):
+        raise NotImplementedError
+
+    def finish_ratios(self):
+        """The table ``(ratio_t, wd_t)`` from ``tsum`` (after the cross-rank sum, where there is one)."""
+        if self.w.is_cuda:
+            rc = _lib.lib().tony_layerwise_ratio(self.layer_kind, self.tsum.data_ptr(), self._adapt.data_ptr(),
+                                                 self.tsum.shape[0], self._hp_dev.data_ptr(), self._ctl_ptr(),
+                                                 self.table.data_ptr(), _lib.stream_ptr(self.w.device))
+            _lib.check(rc, "tony_layerwise_ratio")
+            return
+        if self._skipped_now():
+            return
+        coef, wd = self._coef_now(), _f32(self.weight_decay)
+        for t, ad in enumerate(self.segments.adapt):
+            if not ad:
+                self.table[t, 0], self.table[t, 1] = 1.0, 0.0
+                continue
+            self.table[t, 0] = self._ratio_cpu(self.tsum[t, 0].item(), self.tsum[t, 1].item(), coef)
+            self.table[t, 1] = wd
+
+    def ratios(self) -> torch.Tensor:
+        """The trust ratios of the last ``finish_ratios``, one per tensor (a copy)."""
+        return self.table[:, 0].clone()
+
+    def step(self, grad: torch.Tensor, out_bf16: torch.Tensor | None = None):
+        if grad.numel() != self.w.numel():
+            raise ValueError("grad / shard size mismatch")
+        self.begin_step()
+        if self.needs_norm:
+            self.accumulate_sumsq(grad, 0)
+            self.finish_norm(1)
+        self.norm_range(grad, 0, out_bf16)
+        self.fold_norms()
+        self.finish_ratios()
+        self.apply_range(grad, 0, out_bf16)
+
+    def _ema_cpu(self, lo, n):
+        if self.ema is not None:
+            e = self.ema[lo:lo + n]
+            e.add_((self.w[lo:lo + n] - e) * (1.0 - self._ema_decay_now()))
+
+    def plane_state(self):
+        raise NotImplementedError("LARS and LAMB are not available on the xGMI PS data plane")
+
+
+class FlatLARS(_FlatLayerwise):
+    """LARS in the LARC form over SGD with (Nesterov) momentum: per tensor, with wn = ||w|| and gn = ||g|| (the
+    averaged, clipped gradient), ratio = trust_coef wn / (gn + wd wn + eps) (1 when either norm is 0), then
+    v = mu v + ratio (g + wd w) ; w -= lr v.  Tensors that are not adapted take ratio 1 and no weight decay."""
+
+    n_hp = 8
+    layer_kind = 0
+
+    def __init__(self, master, lr, momentum=0.9, weight_decay=0.0, nesterov=False, trust_coef=0.001, eps=0.0,
+                 segments: Optional[Segments] = None, resync=False, **extra):
+        super().__init__(master, lr, weight_decay, **extra)
+        self.momentum = float(momentum)
+        self.nesterov = bool(nesterov)
+        self.trust_coef = float(trust_coef)
+        self.eps = float(eps)
+        self.resync = bool(resync)
+        self.v = torch.zeros_like(master)
+        self._init_segments(segments)
+
+    def _hp_values(self):
+        return [self.lr, self.momentum, self.weight_decay, self.grad_scale, 1.0 if self.nesterov else 0.0,
+                1.0 if self.resync else 0.0, self.trust_coef, self.eps]
+
+    def _resynced(self, w, out_bf16):
+        if self.resync and out_bf16 is not None and out_bf16.dtype == torch.bfloat16:
+            return torch.where(out_bf16 != w.to(out_bf16.dtype), out_bf16.float(), w)
+        return w
+
+    def norm_range(self, grad: torch.Tensor, lo: int = 0, out_bf16: torch.Tensor | None = None):
+        """The pairs (sum w^2, sum g^2) of master elements [lo, lo + grad.numel()); reads only."""
+        n = self._check_range(grad, lo)
+        if self.w.is_cuda:
+            i0, i1 = self._item_range(lo, n)
+            rc = _lib.lib().tony_lars_norm(self.w.data_ptr(), grad.data_ptr(), int(grad.dtype == torch.bfloat16),
+                                           _lib.ptr(out_bf16), lo, self._items.data_ptr() + 16 * i0, i1 - i0,
+                                           self._item_part.data_ptr() + 8 * i0, self._hp_dev.data_ptr(),
+                                           _lib.stream_ptr(self.w.device))
+            _lib.check(rc, "tony_lars_norm")
+            return
+        for k, a, b, _ in self._segs_in(lo, n):
+            w = self._resynced(self.w[a:b], None if out_bf16 is None else out_bf16[a - lo:b - lo])
+            self._seg_part[k, 0] = w.double().square().sum()
+            self._seg_part[k, 1] = grad[a - lo:b - lo].double().square().sum()
+
+    def _ratio_cpu(self, sw, sg, coef):
+        wn, gn = sw ** 0.5, _f32(self.grad_scale) * coef * sg ** 0.5
+        if not (wn > 0.0 and gn > 0.0):
+            return 1.0
+        return _f32(_f32(self.trust_coef) * wn / (gn + _f32(self.weight_decay) * wn + _f32(self.eps)))
+
+    def apply_range(self, grad: torch.Tensor, lo: int = 0, out_bf16: torch.Tensor | None = None):
+        n = self._check_range(grad, lo)
+        if self.w.is_cuda:
+            i0, i1 = self._item_range(lo, n)
+            rc = _lib.lib().tony_lars_apply(
+                self.w.data_ptr(), self.v.data_ptr(), 0 if self.ema is None else self.ema.data_ptr(),
+                grad.data_ptr(), int(grad.dtype == torch.bfloat16), _lib.ptr(out_bf16), lo,
+                self._items.data_ptr() + 16 * i0, i1 - i0, self.table.data_ptr(), self._hp_dev.data_ptr(),
+                0 if self._xhp_dev is None else self._xhp_dev.data_ptr(), self._ctl_ptr(),
+                _lib.stream_ptr(self.w.device))
+            _lib.check(rc, "tony_lars_apply")
+            return
+        if self._skipped_now():
+            return
+        gsc = _f32(_f32(self.grad_scale) * self._coef_now())
+        for _, a, b, t in self._segs_in(lo, n):
+            ratio, wd = self.table[t, 0].item(), self.table[t, 1].item()
+            w, v = self.w[a:b], self.v[a:b]
+            out = None if out_bf16 is None else out_bf16[a - lo:b - lo]
+            w.copy_(self._resynced(w, out))
+            g = grad[a - lo:b - lo].float() * _f32(gsc * ratio) + _f32(wd * ratio) * w
+            v.mul_(self.momentum).add_(g)
+            w.add_(g + self.momentum * v if self.nesterov else v, alpha=-self.lr)
+            if out is not None:
+                out.copy_(w)
+        self._ema_cpu(lo, n)
+
+    def state_dict(self):
+        return self._extras_state({"kind": "lars", "step": self.step_count, "momentum_buffer": self.v,
+                                   "lr": self.lr})
+
+    def load_state_dict(self, sd):
+        self.step_count = int(sd["step"])
+        self.v.copy_(sd["momentum_buffer"])
+        self.lr = float(sd.get("lr", self.lr))
+        self._load_extras(sd)
+
+
+class FlatLAMB(_FlatLayerwise):
+    """LAMB: Adam's moments with bias correction, u = (m/bc1) / (sqrt(v/bc2) + eps) + wd w, and per tensor
+    ratio = ||w|| / ||u|| (1 when either norm is 0), w -= lr ratio u.  Tensors that are not adapted take ratio 1
+    and no weight decay (plain Adam)."""
+
+    n_hp = 8
+    layer_kind = 1
+
+    def __init__(self, master, lr=1e-3, betas=(0.9, 0.999), eps=1e-6, weight_decay=0.0,
+                 segments: Optional[Segments] = None, **extra):
+        super().__init__(master, lr, weight_decay, **extra)
+        self.b1, self.b2 = float(betas[0]), float(betas[1])
+        self.eps = float(eps)
+        self.m = torch.zeros_like(master)
+        self.v = torch.zeros_like(master)
+        self._init_segments(segments)
+
+    def _hp_values(self):
+        t = self.step_count
+        return [self.lr, self.b1, self.b2, self.eps, self.weight_decay, self.grad_scale, 1.0 - self.b1 ** t,
+                1.0 - self.b2 ** t]
+
+    def _u_cpu(self, a, b, wd):
+        t = self.step_count
+        bc1, bc2 = 1.0 - self.b1 ** t, 1.0 - self.b2 ** t
+        return (self.m[a:b] / bc1) / ((self.v[a:b] / bc2).sqrt() + self.eps) + wd * self.w[a:b]
+
+    def norm_range(self, grad: torch.Tensor, lo: int = 0, out_bf16: torch.Tensor | None = None):
+        """The moment update of master elements [lo, lo + grad.numel()) and their pairs (sum w^2, sum u^2); with
+        ``clip_norm`` / ``skip_nonfinite`` it needs ``finish_norm`` first (it reads the coefficient and the skip)."""
+        n = self._check_range(grad, lo)
+        if self.w.is_cuda:
+            i0, i1 = self._item_range(lo, n)
+            rc = _lib.lib().tony_lamb_norm(self.w.data_ptr(), self.m.data_ptr(), self.v.data_ptr(), grad.data_ptr(),
+                                           int(grad.dtype == torch.bfloat16), lo, self._items.data_ptr() + 16 * i0,
+                                           i1 - i0, self._adapt.data_ptr(), self._item_part.data_ptr() + 8 * i0,
+                                           self._hp_dev.data_ptr(), self._ctl_ptr(), _lib.stream_ptr(self.w.device))
+            _lib.check(rc, "tony_lamb_norm")
+            return
+        if self._skipped_now():
+            return
+        gsc = _f32(_f32(self.grad_scale) * self._coef_now())
+        for k, a, b, t in self._segs_in(lo, n):
+            g = grad[a - lo:b - lo].float() * gsc
+            self.m[a:b].mul_(self.b1).add_(g, alpha=1 - self.b1)
+            self.v[a:b].mul_(self.b2).addcmul_(g, g, value=1 - self.b2)
+            u = self._u_cpu(a, b, _f32(self.weight_decay) if self.segments.adapt[t] else 0.0)
+            self._seg_part[k, 0] = self.w[a:b].double().square().sum()
+            self._seg_part[k, 1] = u.double().square().sum()
+
+    def _ratio_cpu(self, sw, su, coef):
+        wn, un = sw ** 0.5, su ** 0.5
+        return _f32(wn / un) if wn > 0.0 and un > 0.0 else 1.0
+
+    def apply_range(self, grad: torch.Tensor, lo: int = 0, out_bf16: torch.Tensor | None = None):
+        """``w -= lr ratio_t u`` over master elements [lo, lo + grad.numel()): the gradient itself was consumed by
+        ``norm_range`` and is not read again."""
+        n = self._check_range(grad, lo)
+        if self.w.is_cuda:
+            i0, i1 = self._item_range(lo, n)
+            rc = _lib.lib().tony_lamb_apply(
+                self.w.data_ptr(), self.m.data_ptr(), self.v.data_ptr(),
+                0 if self.ema is None else self.ema.data_ptr(), _lib.ptr(out_bf16), lo,
+                self._items.data_ptr() + 16 * i0, i1 - i0, self.table.data_ptr(), self._hp_dev.data_ptr(),
+                0 if self._xhp_dev is None else self._xhp_dev.data_ptr(), self._ctl_ptr(),
+                _lib.stream_ptr(self.w.device))
+            _lib.check(rc, "tony_lamb_apply")
+            return
+        if self._skipped_now():
+            return
+        for _, a, b, t in self._segs_in(lo, n):
+            ratio, wd = self.table[t, 0].item(), self.table[t, 1].item()
+            self.w[a:b].add_(self._u_cpu(a, b, wd), alpha=-_f32(_f32(self.lr) * ratio))
+            if out_bf16 is not None:
+                out_bf16[a - lo:b - lo].copy_(self.w[a:b])
+        self._ema_cpu(lo, n)
+
+    def state_dict(self):
+        return self._extras_state({"kind": "lamb", "step": self.step_count, "exp_avg": self.m, "exp_avg_sq": self.v,
+                                   "lr": self.lr})
+
+    def load_state_dict(self, sd):
+        self.step_count = int(sd["step"])
+        self.m.copy_(sd["exp_avg"])
+        self.v.copy_(sd["exp_avg_sq"])
+        self.lr = float(sd.get("lr", self.lr))
+        self._load_extras(sd)
 
 
 def grad_stats(grad: torch.Tensor):

@@ -10,6 +10,7 @@ in the HIP kernels need multiples of 8 bf16).
 """
 from __future__ import annotations
 
+import bisect
 from dataclasses import dataclass
 
 import torch
@@ -81,3 +82,37 @@ class FlatParams:
 
     def master_copy(self, rank: int = 0) -> torch.Tensor:
         return self.shard(self.data, rank).float().clone()
+
+
+def build_segments(flat: FlatParams, ranges, adapt_filter=None):
+    """The ``Segments`` table (ops/optim.py) of a master shard made of the flat ranges ``ranges`` -- ``(flat_lo,
+    flat_hi)`` pairs laid end to end in master order: the whole buffer for Horovod, the one-rank PS and the async
+    ps, the owned buckets of a dedicated ps task, rank r's piece of every bucket for the colocated PS.
+
+    Tensor ids are slot indices, the same on every rank, so a tensor cut by a piece boundary gives segments on two
+    ranks that carry one id.  A slot's alignment padding (and the buffer's tail padding) belongs to the slot before
+    it: it is zero in the variables and in the gradient and stays zero.  Every range begins a new segment, so the
+    ranges are also what ``norm_range`` / ``apply_range`` may be called with.
+
+    ``adapt``: parameters with ``ndim <= 1`` (BatchNorm scale and shift, biases) take no trust ratio and no weight
+    decay, the usual LARS / LAMB exclusion; ``adapt_filter(name, param) -> bool`` overrides the rule."""
+    from ..ops.optim import Segments
+
+    offs = [s.offset for s in flat.slots]
+    ends = offs[1:] + [flat.numel]  # padding attributed to the slot before it
+    starts, tensor, m = [0], [], 0
+    for lo, hi in ranges:
+        if not 0 <= lo < hi <= flat.numel or lo % 4 or hi % 4:
+            raise ValueError(f"master range [{lo}, {hi}) is empty, outside the flat buffer or not 4-aligned")
+        i = bisect.bisect_right(offs, lo) - 1
+        while i < len(offs) and offs[i] < hi:
+            a, b = max(lo, offs[i]), min(hi, ends[i])
+            m += b - a
+            starts.append(m)
+            tensor.append(i)
+            i += 1
+    if adapt_filter is None:
+        adapt = [len(s.shape) > 1 for s in flat.slots]
+    else:
+        adapt = [bool(adapt_filter(s.name, p)) for s, p in zip(flat.slots, flat.params)]
+    return Segments(starts, tensor, adapt, [s.name for s in flat.slots])

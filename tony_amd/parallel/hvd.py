@@ -325,6 +325,9 @@ def broadcast_optimizer_state(optimizer: torch.optim.Optimizer, root_rank: int =
 
 _CLIP_NEEDS_FUSED = ("clip_norm is applied by the fused HIP optimizers only: pass fused=True (a single-group SGD, "
                      "Adam, AdamW, Adagrad or RMSprop on GPU tensors), or clip before step() yourself")
+_LAYERWISE_NEEDS_FUSED = ("lars_coef and lamb are applied by the fused HIP optimizers only: pass fused=True "
+                          "(lars_coef: a single-group torch.optim.SGD; lamb: a single-group torch.optim.AdamW, on "
+                          "GPU tensors)")
 _NEEDS_SGD = "fused=True needs a single-group, dampening-free torch.optim.SGD on GPU tensors"
 
 
@@ -361,10 +364,18 @@ class _DistributedOptimizer:
     def __init__(self, optimizer, named_parameters=None, compression=Compression.none,
                  backward_passes_per_step: int = 1, op=Average, bucket_mb: float = DEFAULT_BUCKET_MB,
                  gradient_predivide_factor: float = 1.0, fused: Optional[bool] = None,
-                 clip_norm: Optional[float] = None):
+                 clip_norm: Optional[float] = None, lars_coef: Optional[float] = None, lamb: bool = False,
+                 adapt_filter=None):
         _need_init()
         if clip_norm is not None and fused is False:
             raise ValueError(_CLIP_NEEDS_FUSED)
+        if (lars_coef is not None or lamb) and not fused:
+            raise ValueError(_LAYERWISE_NEEDS_FUSED)
+        if lamb and not isinstance(optimizer, torch.optim.AdamW):
+            raise ValueError("lamb=True needs a torch.optim.AdamW (LAMB's weight decay is decoupled from the moments, "
+                             f"as AdamW's is), got torch.optim.{type(optimizer).__name__}")
+        if lars_coef is not None and not isinstance(optimizer, torch.optim.SGD):
+            raise ValueError(f"lars_coef needs a torch.optim.SGD, got torch.optim.{type(optimizer).__name__}")
         if op not in (Average, Sum):
             raise ValueError("DistributedOptimizer supports op=Average or op=Sum")
         self.optimizer = optimizer
@@ -398,10 +409,10 @@ class _DistributedOptimizer:
         # fused apply: a single-group torch SGD on GPU tensors becomes ONE fused HIP SGD-momentum launch
         # per flat buffer (fp32 master + momentum, writes the bf16 compute copy; ops/optim.py)
         self._fused = []
-        can_fuse = (isinstance(optimizer, torch.optim.SGD) and len(optimizer.param_groups) == 1
-                    and all(f.device.type == "cuda" for f, _ in self.groups)
-                    and not optimizer.param_groups[0].get("dampening", 0)
-                    and not optimizer.param_groups[0].get("maximize", False))
+        sgd_ok = (isinstance(optimizer, torch.optim.SGD) and len(optimizer.param_groups) == 1
+                  and not optimizer.param_groups[0].get("dampening", 0)
+                  and not optimizer.param_groups[0].get("maximize", False))
+        can_fuse = sgd_ok and all(f.device.type == "cuda" for f, _ in self.groups)
         # an explicit fused=True also takes a single-group Adam / AdamW / Adagrad / RMSprop over fp32 GPU
         # parameters (the flat buffer is then the master: nothing to resync); fused=None auto-fuses SGD only
         self._kind = "sgd"
@@ -409,6 +420,8 @@ class _DistributedOptimizer:
             fused = can_fuse
             if clip_norm is not None and not fused:
                 raise ValueError(_CLIP_NEEDS_FUSED)
+        elif fused and lars_coef is not None and sgd_ok:
+            pass  # FlatLARS also runs on CPU tensors (its torch fallback): local and gloo runs of a LARS job
         elif fused and not can_fuse:
             if not isinstance(optimizer, (torch.optim.Adam, torch.optim.AdamW, torch.optim.Adagrad,
                                           torch.optim.RMSprop)):
@@ -418,12 +431,26 @@ class _DistributedOptimizer:
         # block per group, folded together on the device (ops/optim.py), then each group's clipped apply
         self._clip = clip_norm is not None
         xkw = {"clip_norm": clip_norm} if self._clip else {}
+        # lars_coef / lamb: the same wrapped classes, each parameter tensor's update scaled by its own trust ratio
+        # (ops/optim.py FlatLARS / FlatLAMB; parameters with ndim <= 1 are not adapted unless adapt_filter says so)
+        self._layerwise = lars_coef is not None or bool(lamb)
+        if self._layerwise:
+            from .flat import build_segments
+
+            # the flat buffers name their slots p0, p1, ...: an adapt_filter sees the names of named_parameters
+            names = {id(p): n for n, p in named} if named_parameters is not None else {}
+            by_name = None if adapt_filter is None else (lambda n, p: adapt_filter(names.get(id(p), n), p))
+
+            def seg_kw(flat):
+                return dict(segments=build_segments(flat, [(0, flat.numel)], by_name), **xkw)
         if fused and self._kind != "sgd":
-            from ..ops.optim import FlatAdagrad, FlatAdam, FlatRMSProp
+            from ..ops.optim import FlatAdagrad, FlatAdam, FlatLAMB, FlatRMSProp
 
             g = optimizer.param_groups[0]
             for flat, _ in self.groups:
-                if self._kind == "adam":
+                if lamb:
+                    fo = FlatLAMB(flat.data, float(g["lr"]), **seg_kw(flat))
+                elif self._kind == "adam":
                     fo = FlatAdam(flat.data, float(g["lr"]), **xkw)
                 elif self._kind == "adagrad":
                     fo = FlatAdagrad(flat.data, float(g["lr"]),
@@ -433,13 +460,19 @@ class _DistributedOptimizer:
                 self._fused.append((flat, fo))
             self._sync_hp()
         elif fused:
-            from ..ops.optim import FlatSGD
+            from ..ops.optim import FlatLARS, FlatSGD
 
             g = optimizer.param_groups[0]
             for flat, _ in self.groups:
                 # an fp32 flat buffer IS the master (nothing to keep in sync); a bf16 one gets an fp32
                 # master that re-seeds from any element changed behind the optimizer's back (resync)
                 master = flat.data if flat.data.dtype == torch.float32 else flat.data.float().clone()
+                if lars_coef is not None:
+                    self._fused.append((flat, FlatLARS(master, g["lr"], momentum=g["momentum"],
+                                                       weight_decay=g["weight_decay"], nesterov=g["nesterov"],
+                                                       trust_coef=float(lars_coef), resync=master is not flat.data,
+                                                       **seg_kw(flat))))
+                    continue
                 self._fused.append((flat, FlatSGD(master, g["lr"], momentum=g["momentum"],
                                                   weight_decay=g["weight_decay"], nesterov=g["nesterov"],
                                                   resync=master is not flat.data, **xkw)))
@@ -587,6 +620,10 @@ class _DistributedOptimizer:
         for flat, opt in self._fused:
             if not self._clip:
                 opt.begin_step()
+            if self._layerwise:  # one rank holds every tensor whole: the three norm stages, then the apply
+                opt.norm_range(flat.grad, 0, None if opt.w is flat.data else flat.data)
+                opt.fold_norms()
+                opt.finish_ratios()
             # an fp32 flat buffer is the master, updated in place; a bf16 one is the compute copy of SGD's master
             opt.apply_range(flat.grad, 0, None if opt.w is flat.data else flat.data)
         return loss
@@ -600,7 +637,9 @@ def DistributedOptimizer(optimizer, named_parameters=None, compression=Compressi
     """Horovod's DistributedOptimizer: bucketed gradient averaging overlapped with backward; a plain
     torch SGD on GPU tensors is applied by the fused HIP kernel (``fused=False`` keeps torch's); ``fused=True``
     also takes a single-group Adam / AdamW / Adagrad / RMSprop over fp32 GPU parameters.  ``clip_norm`` (fused
-    only) clips the averaged gradient by its global norm over all parameters before the apply."""
+    only) clips the averaged gradient by its global norm over all parameters before the apply.  ``lars_coef``
+    (with a torch SGD) and ``lamb=True`` (with a torch AdamW), fused only, scale every parameter tensor's update by
+    its trust ratio (LARS / LAMB); ``adapt_filter(name, param)`` overrides which tensors are adapted."""
     return _DistributedOptimizer(optimizer, named_parameters, compression, backward_passes_per_step, op, **kw)
 
 

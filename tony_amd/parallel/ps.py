@@ -54,6 +54,13 @@ all compute the identical coefficient.  Clipping therefore trades the overlap of
 the global norm (the pushes still overlap).  The xGMI data plane applies chunk by chunk as rows land, before any
 norm can exist: it refuses these options (use ``plane="rccl"``).
 
+``optimizer="lars"`` / ``"lamb"`` (per-tensor trust ratios, ops/optim.py FlatLARS / FlatLAMB) take the same deferred
+path: each bucket's per-tensor partial norms are taken when the bucket is pushed, at the end of backward ONE small
+all-reduce sums the per-tensor array over the shard holders (a tensor cut by a piece boundary lies on two ranks), each
+owner forms the identical ratio table on its device, then the buckets are applied and pulled in bucket order.
+Parameters with ``ndim <= 1`` take no trust ratio and no weight decay (``adapt_filter(name, param)`` overrides).  The
+xGMI data plane refuses these kinds too.
+
 ``ema_weights()`` swaps the EMA into the variables for an evaluation and restores them afterwards.
 """
 from __future__ import annotations
@@ -67,13 +74,14 @@ from typing import Dict, List, Optional
 import torch
 import torch.distributed as dist
 
-from ..ops.optim import SUMSQ_BLOCKS, FlatAdagrad, FlatAdam, FlatRMSProp, FlatSGD
+from ..ops.optim import SUMSQ_BLOCKS, FlatAdagrad, FlatAdam, FlatLAMB, FlatLARS, FlatRMSProp, FlatSGD
 from . import collectives as coll
 from .buckets import DEFAULT_BUCKET_MB, Bucket, GradBucketEngine, make_buckets
-from .flat import FlatParams
+from .flat import FlatParams, build_segments
 
 
 _EXTRAS = ("clip_norm", "skip_nonfinite", "ema_decay", "ema_warmup")
+_LAYERWISE = ("lars", "lamb")
 
 
 def make_optimizer(kind: str, master: torch.Tensor, lr: float, momentum: float = 0.9, weight_decay: float = 0.0,
@@ -82,7 +90,9 @@ def make_optimizer(kind: str, master: torch.Tensor, lr: float, momentum: float =
     ``rmsprop`` (torch's form) and ``rmsprop_tf`` (TF's form, the Inception-v3 recipe).  ``momentum`` goes to SGD and
     to both RMSProp kinds; ``eps``, ``alpha`` and ``initial_accumulator_value`` come from ``kw``.  ``rmsprop_tf``'s
     ``eps`` defaults to 1.0, the Inception recipe's value (RMSProp decay 0.9, momentum 0.9, epsilon 1.0), so that
-    ``bench.py --optimizer rmsprop_tf``, which passes no ``eps``, trains with that recipe."""
+    ``bench.py --optimizer rmsprop_tf``, which passes no ``eps``, trains with that recipe.  ``lars`` (over SGD with
+    momentum) and ``lamb`` (over Adam) scale every parameter tensor's update by its trust ratio: they take
+    ``segments`` (where the tensors lie in ``master``; None: one tensor) and ``trust_coef`` (LARS)."""
     kind = kind.lower()
     # clip_norm / skip_nonfinite / ema_decay / ema_warmup: every kind takes them (ops/optim.py _FlatOptimizer)
     extra = {k: kw[k] for k in _EXTRAS if k in kw}
@@ -101,6 +111,13 @@ def make_optimizer(kind: str, master: torch.Tensor, lr: float, momentum: float =
         return FlatRMSProp(master, lr, alpha=kw.get("alpha", 0.9), momentum=momentum,
                            eps=kw.get("eps", 1.0 if tf_style else 1e-8), weight_decay=weight_decay, tf_style=tf_style,
                            **extra)
+    if kind == "lars":
+        return FlatLARS(master, lr, momentum=momentum, weight_decay=weight_decay, nesterov=kw.get("nesterov", False),
+                        trust_coef=kw.get("trust_coef", 0.001), eps=kw.get("eps", 0.0), segments=kw.get("segments"),
+                        **extra)
+    if kind == "lamb":
+        return FlatLAMB(master, lr, betas=kw.get("betas", (0.9, 0.999)), eps=kw.get("eps", 1e-6),
+                        weight_decay=weight_decay, segments=kw.get("segments"), **extra)
     raise ValueError(f"unknown optimizer {kind!r}")
 
 
@@ -118,7 +135,16 @@ class ParameterServer:
                  group=None, dtype=torch.bfloat16, device=None, wire_dtype: Optional[torch.dtype] = None,
                  bucket_mb: float = DEFAULT_BUCKET_MB, bucketed_single: bool = False, plane: str = "auto",
                  clip_norm: Optional[float] = None, skip_nonfinite: bool = False, ema_decay: Optional[float] = None,
-                 ema_warmup: bool = False, **opt_kw):
+                 ema_warmup: bool = False, trust_coef: float = 0.001, adapt_filter=None, **opt_kw):
+        # lars / lamb: per-tensor trust ratios.  Each optimizer gets the table of where the tensors lie in its
+        # master shard; the step is deferred like a clipped one whenever buckets are in play (see _finish_norm)
+        self.layerwise = optimizer.lower() in _LAYERWISE
+        self._lamb = optimizer.lower() == "lamb"
+        self._adapt_filter = adapt_filter
+        if self.layerwise:
+            if optimizer.lower() == "lars":
+                opt_kw["trust_coef"] = trust_coef
+            self._refuse_plane_layerwise(model, mode, plane, device, group)  # before any tensor is made
         self.needs_norm = clip_norm is not None or bool(skip_nonfinite)
         self.has_ema = ema_decay is not None
         if self.needs_norm or self.has_ema:
@@ -169,7 +195,9 @@ class ParameterServer:
                 pieces.append(f.data[b.lo + self.rank * p:b.lo + (self.rank + 1) * p])
                 m += p
             master = torch.cat(pieces).float()
-            opt = make_optimizer(optimizer, master, lr, momentum, weight_decay, **opt_kw)
+            ranges = [(b.lo + self.rank * (b.numel // n_split), b.lo + (self.rank + 1) * (b.numel // n_split))
+                      for b in sorted(self.buckets, key=lambda b: b.lo)]
+            opt = make_optimizer(optimizer, master, lr, momentum, weight_decay, **self._seg_kw(ranges), **opt_kw)
             opt.grad_scale = 1.0 / len(self.worker_ranks)
             self.optimizers[self.rank] = opt
             self._gshard = torch.zeros(m, dtype=self.wire_dtype, device=f.device) if self.world > 1 else None
@@ -182,12 +210,14 @@ class ParameterServer:
                     m += b.numel
             if pieces:
                 master = torch.cat(pieces).float()
-                opt = make_optimizer(optimizer, master, lr, momentum, weight_decay, **opt_kw)
+                ranges = [(b.lo, b.hi) for b in self.buckets if self._owner(b) == self.rank]
+                opt = make_optimizer(optimizer, master, lr, momentum, weight_decay, **self._seg_kw(ranges), **opt_kw)
                 opt.grad_scale = 1.0 / len(self.worker_ranks)
                 self.optimizers[self.rank] = opt
         else:  # asynchronous: the single ps task owns the whole buffer (masters in flat order)
             if self.is_ps:
-                opt = make_optimizer(optimizer, f.data.float().clone(), lr, momentum, weight_decay, **opt_kw)
+                opt = make_optimizer(optimizer, f.data.float().clone(), lr, momentum, weight_decay,
+                                     **self._seg_kw([(0, f.numel)]), **opt_kw)
                 self.optimizers[self.rank] = opt
                 for b in self.buckets:
                     self._master_range[b.index] = (b.lo, b.numel)
@@ -223,9 +253,10 @@ class ParameterServer:
                 for opt in self.optimizers.values():
                     opt.grad_scale = 1.0 / len(self.worker_ranks) if sync else 1.0
         # a global norm: one partial block per bucket, applies and pulls deferred to the end of backward
-        self._norm_deferred = self.needs_norm and self.plane is None
+        # (a trust ratio defers the same way: a tensor's norm may be spread over the ranks)
+        self._norm_deferred = (self.needs_norm or self.layerwise) and self.plane is None
         self._foreign_blocks = None
-        if self._norm_deferred:
+        if self._norm_deferred and self.needs_norm:
             for opt in self.optimizers.values():
                 opt.partials(len(self.buckets))
             foreign = [b.index for b in self.buckets if self._master_range[b.index] is None]
@@ -256,6 +287,52 @@ class ParameterServer:
             raise ValueError("clip_norm, skip_nonfinite and ema_decay are not available on the xGMI PS data plane: "
                              "it applies chunk by chunk as the workers' rows land, before a global norm exists, and "
                              "keeps no EMA; construct the ParameterServer with plane=\"rccl\"")
+
+    @staticmethod
+    def _refuse_plane_layerwise(model, mode, plane, device, group):
+        """optimizer="lars" / "lamb" on the xGMI data plane: refused like ``_refuse_plane_extras``."""
+        want = plane
+        if plane == "auto" and mode == "dedicated" and coll.world(group) > 1:
+            dev = torch.device(device) if device is not None else next(model.parameters()).device
+            want = os.environ.get("TONY_PS_PLANE", "xgmi") if dev.type == "cuda" else "rccl"
+        if want == "xgmi":
+            raise ValueError("the lars and lamb optimizers are not available on the xGMI PS data plane: it applies "
+                             "chunk by chunk as the workers' rows land, before any tensor's norm exists; construct "
+                             "the ParameterServer with plane=\"rccl\"")
+
+    def _seg_kw(self, ranges) -> dict:
+        """``segments=`` for a lars / lamb optimizer whose master is the flat ranges ``ranges`` laid end to end."""
+        if not self.layerwise:
+            return {}
+        return {"segments": build_segments(self.flat, ranges, self._adapt_filter)}
+
+    def _bucket_norms(self, opt, grad: torch.Tensor, b: Bucket, m: int):
+        """Bucket b is pushed (``grad``: what this rank holds of it, master offset ``m``): its share of the global
+        norm and of the per-tensor norms.  LAMB's norm pass reads the clip coefficient, so with a global norm it
+        waits for ``_finish_norm``."""
+        if self.needs_norm:
+            opt.accumulate_sumsq(grad, b.index)
+        if self.layerwise and not (self._lamb and self.needs_norm):
+            opt.norm_range(grad, m)
+
+    def _whole_norms(self, opt, grad: torch.Tensor):
+        """The norm stages of a step that applies the whole buffer at once."""
+        if self.needs_norm:
+            opt.accumulate_sumsq(grad, 0)
+            opt.finish_norm(1)
+        if self.layerwise:
+            opt.norm_range(grad, 0)
+            opt.fold_norms()
+            opt.finish_ratios()
+
+    def _pushed(self, b: Bucket):
+        """(gradient, master offset) of what this rank owns of bucket b after its push, or None."""
+        if self._master_range[b.index] is None:
+            return None
+        m, p = self._master_range[b.index]
+        if self.mode == "colocated":
+            return (self.flat.grad[b.lo:b.hi] if self.world == 1 else self._gshard[m:m + p]), m
+        return self._wire_grad_view(b), m
 
     def zero_grad(self):
         self.flat.zero_grad()
@@ -306,9 +383,7 @@ class ParameterServer:
                 self.begin_step()
             self._begun = False
             opt = self.optimizers[self.rank]
-            if self.needs_norm:  # begin_step pushed the hyper-parameters: norm, then the one fused apply
-                opt.accumulate_sumsq(self.flat.grad, 0)
-                opt.finish_norm(1)
+            self._whole_norms(opt, self.flat.grad)  # begin_step pushed the hyper-parameters
             self._apply(opt, self.flat.grad, 0, self.flat.data)
             self.steps += 1
             return
@@ -367,7 +442,7 @@ class ParameterServer:
             own = f.data[b.lo + self.rank * p:b.lo + (self.rank + 1) * p]
             if self.world == 1:
                 if self._norm_deferred:
-                    opt.accumulate_sumsq(f.grad[b.lo:b.hi], b.index)
+                    self._bucket_norms(opt, f.grad[b.lo:b.hi], b, m)
                     return
                 self._apply(opt, f.grad[b.lo:b.hi], m, own)
                 return
@@ -375,7 +450,7 @@ class ParameterServer:
             gs = self._gshard[m:m + p]
             _wait(coll.reduce_scatter_flat(gs, g, group=self.group, async_op=True))     # push
             if self._norm_deferred:  # the piece's share of the global norm; apply + pull in _finish_norm
-                opt.accumulate_sumsq(gs, b.index)
+                self._bucket_norms(opt, gs, b, m)
                 self.push_bytes += g.numel() * g.element_size()
                 return
             self._apply(opt, gs, m, own)                                                  # apply (HIP)
@@ -387,7 +462,7 @@ class ParameterServer:
         _wait(dist.reduce(g, dst=owner, group=self.group, async_op=True))                # push
         if self._norm_deferred:
             if self.rank == owner:
-                opt.accumulate_sumsq(g, b.index)
+                self._bucket_norms(opt, g, b, self._master_range[b.index][0])
             if self.is_worker:
                 self.push_bytes += g.numel() * g.element_size()
             return
@@ -399,22 +474,37 @@ class ParameterServer:
             self.push_bytes += g.numel() * g.element_size()
 
     def _finish_norm(self):
-        """End of backward with a global norm (the communication stream is current): every bucket is pushed and
-        its owner's partial block written.  Sum the blocks over the ranks, fold them into the coefficient, then
-        apply and pull every bucket in bucket order."""
+        """End of backward with a global norm and / or per-tensor trust ratios (the communication stream is
+        current): every bucket is pushed and its owner's partial block written.  Sum the blocks over the ranks, fold
+        them into the coefficient (then the same for the per-tensor sums and the ratio table), then apply and pull
+        every bucket in bucket order."""
         f = self.flat
         opt = self.optimizers.get(self.rank)
         nb = len(self.buckets)
-        if len(self.ps_ranks) > 1:
+        if self.needs_norm and len(self.ps_ranks) > 1:
             # more than one rank holds pieces.  A block is zero on a rank that owns nothing of its bucket, and a
             # rank without a shard (a dedicated worker) contributes zeros, so the sum is every piece's block once
             part = opt.partials(nb) if opt is not None else torch.zeros(nb * SUMSQ_BLOCKS, dtype=torch.float32,
                                                                         device=f.device)
             _wait(coll.all_reduce(part, group=self.group, async_op=True))
-        if opt is not None:
+        if opt is not None and self.needs_norm:
             opt.finish_norm(nb)
             if self._foreign_blocks is not None:  # the other owners' blocks: zero again for the next step's sum
                 opt.partials(nb).view(nb, SUMSQ_BLOCKS).index_fill_(0, self._foreign_blocks, 0.0)
+        if self.layerwise:
+            # per-tensor norms: every owner folds its items into tsum[T][2]; a tensor cut by a piece boundary (or
+            # owned elsewhere) is completed by ONE all-reduce of that array, so every rank forms the same ratios
+            if opt is not None and self._lamb and self.needs_norm:
+                for b in self.buckets:
+                    got = self._pushed(b)
+                    if got is not None:
+                        opt.norm_range(got[0], got[1])
+            tsum = opt.fold_norms() if opt is not None else torch.zeros(len(f.slots), 2, dtype=torch.float32,
+                                                                       device=f.device)
+            if len(self.ps_ranks) > 1:
+                _wait(coll.all_reduce(tsum, group=self.group, async_op=True))
+            if opt is not None:
+                opt.finish_ratios()
         for b in self.buckets:
             if self.mode == "colocated":
                 m, p = self._master_range[b.index]
@@ -445,9 +535,7 @@ class ParameterServer:
     def _step_whole(self, opt, grad: torch.Tensor):
         """One whole-buffer update (the async ps applies each push on its own, norm included)."""
         opt.begin_step()
-        if self.needs_norm:
-            opt.accumulate_sumsq(grad, 0)
-            opt.finish_norm(1)
+        self._whole_norms(opt, grad)
         self._apply(opt, grad, 0, self.flat.data)
 
     def _step_dedicated_async_worker(self):
