@@ -61,9 +61,15 @@ __global__ __launch_bounds__(kThreads) void xent_fwd_kernel(const void* __restri
   if (threadIdx.x == 0) {
     const float lse = mx + __logf(se);
     const int64_t t = labels[row];
-    const float xt = (t >= 0 && t < K) ? ld<kBf16>(logits, base + t) : lse;
-    // loss = -(1-s) * log p_t - s/K * sum_k log p_k
-    loss[row] = (1.f - smoothing) * (lse - xt) + smoothing * (lse - sx / static_cast<float>(K));
+    // a label outside [0, K) marks an ignored row: loss 0 (and a zero gradient row in the backward),
+    // lse still stored
+    const bool live = t >= 0 && t < K;
+    const float xt = live ? ld<kBf16>(logits, base + t) : lse;
+    // loss = -(1-s) * log p_t - s/K * sum_k log p_k.  Without smoothing the second term is left out, not
+    // multiplied by 0: a class masked with -inf makes sum_k x_k -inf, and 0 * inf would turn the loss into NaN
+    float l = (1.f - smoothing) * (lse - xt);
+    if (smoothing != 0.f) l += smoothing * (lse - sx / static_cast<float>(K));
+    loss[row] = live ? l : 0.f;
     lse_out[row] = lse;
   }
 }
@@ -78,11 +84,12 @@ __global__ __launch_bounds__(kThreads) void xent_bwd_kernel(const void* __restri
   const float l = lse[row];
   const float go = gout[row];
   const int64_t t = labels[row];
+  const bool live = t >= 0 && t < K;  // else an ignored row (the forward's loss is 0): zero gradient
   const float off = smoothing / static_cast<float>(K);
   for (int k = threadIdx.x; k < K; k += kThreads) {
     const float p = __expf(ld<kBf16>(logits, row * ld_ + k) - l);
     const float target = (k == t ? 1.f - smoothing : 0.f) + off;
-    const float d = (p - target) * go;
+    const float d = live ? (p - target) * go : 0.f;
     if constexpr (kBf16)
       static_cast<uint16_t*>(dlogits)[row * ldd + k] = f2bf(d);
     else
@@ -96,6 +103,7 @@ TONY_API int tony_xent_fwd(const void* logits, int is_bf16, int64_t N, int K, in
                            const int64_t* labels, float smoothing, float* loss, float* lse,
                            hipStream_t stream) {
   if (K <= 0 || K > kThreads * kPerThread) return -1;
+  if (N <= 0) return 0;
   if (is_bf16)
     xent_fwd_kernel<true><<<N, kThreads, 0, stream>>>(logits, ld_, K, labels, smoothing, loss, lse);
   else
@@ -108,6 +116,7 @@ TONY_API int tony_xent_bwd(const void* logits, int is_bf16, int64_t N, int K, in
                            const int64_t* labels, float smoothing, const float* lse, const float* gout,
                            void* dlogits, int64_t ldd, hipStream_t stream) {
   if (K <= 0) return -1;
+  if (N <= 0) return 0;
   if (is_bf16)
     xent_bwd_kernel<true><<<N, kThreads, 0, stream>>>(logits, ld_, K, labels, smoothing, lse, gout, dlogits, ldd);
   else

@@ -44,11 +44,20 @@ class _XentFn(torch.autograd.Function):
 
 def cross_entropy(logits: torch.Tensor, labels: torch.Tensor, label_smoothing: float = 0.0,
                   reduction: str = "mean") -> torch.Tensor:
-    """Softmax cross-entropy; per-row losses are fp32 whatever the logits dtype."""
+    """Softmax cross-entropy; per-row losses are fp32 whatever the logits dtype.
+
+    A label outside ``[0, K)`` (``-100``, ``K``, ...) marks an ignored row: its loss is 0 and its gradient row
+    is 0, whatever the smoothing -- per row what ``F.cross_entropy(ignore_index=t)`` gives.  Unlike torch,
+    ``reduction="mean"`` divides by the number of rows ``N``, ignored rows included.  ``N = 0`` is accepted
+    (sum 0, an empty gradient; the mean of no rows is NaN as in torch).  Classes masked with ``-inf`` keep a
+    finite loss without smoothing (with smoothing the loss of such a row is +inf by definition) and get the
+    finite gradient ``-(smoothing / K) * gout``.  ``K`` is at most 4096."""
     if logits.is_cuda:
         per_row = _XentFn.apply(logits, labels, label_smoothing)
     else:
-        per_row = torch.nn.functional.cross_entropy(logits.float(), labels, reduction="none",
+        valid = (labels >= 0) & (labels < logits.shape[1])  # the same ignored rows as the kernels
+        per_row = torch.nn.functional.cross_entropy(logits.float(), torch.where(valid, labels, -100),
+                                                    reduction="none", ignore_index=-100,
                                                     label_smoothing=label_smoothing)
     if reduction == "mean":
         return per_row.mean()
