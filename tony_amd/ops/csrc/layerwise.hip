@@ -14,7 +14,7 @@
 //   ratio       table[T] = (ratio_t, wd_t), formed in double and rounded once; non-adapted tensors get (1, 0)
 //   apply       LARS: sgd_update4 with gs' = gs coef ratio_t, wd' = wd_t ratio_t  (v = mu v + ratio (g + wd w))
 //               LAMB: w -= lr ratio_t u, u recomputed from the stored m, v and the old w
-// with the EMA beside the master, the bf16 compute copy and the non-finite skip of optim.hip's apply_x.
+// with the EMA beside the master, the bf16 compute copy and the non-finite skip of optim.hip's tony_optim_apply_x.
 //   LARS hp = [lr, momentum, weight_decay, grad_scale, nesterov, resync, trust_coef, eps]   (SGD's six first)
 //   LAMB hp = [lr, beta1, beta2, eps, weight_decay, grad_scale, bias_corr1, bias_corr2]
 //   xhp, ctl: as in optim.hip (ctl = [coef, skip, norm, skipped steps]; nullptr: coef 1, no skip)
@@ -30,53 +30,6 @@ namespace {
 constexpr int kThreads = 256;
 constexpr int kItemFloats = 4096;  // 4 float4 per thread: ~6,600 workgroups for the 27M-parameter shard
 constexpr int kFoldThreads = 64;
-
-template <bool kGradBf16>
-__device__ __forceinline__ void load_grad4(const void* g, int64_t i, float* out) {
-  if constexpr (kGradBf16) {
-    const uint2 v = *reinterpret_cast<const uint2*>(static_cast<const uint16_t*>(g) + i);
-    out[0] = __uint_as_float(v.x << 16);
-    out[1] = __uint_as_float(v.x & 0xffff0000u);
-    out[2] = __uint_as_float(v.y << 16);
-    out[3] = __uint_as_float(v.y & 0xffff0000u);
-  } else {
-    const float4 v = *reinterpret_cast<const float4*>(static_cast<const float*>(g) + i);
-    out[0] = v.x;
-    out[1] = v.y;
-    out[2] = v.z;
-    out[3] = v.w;
-  }
-}
-
-__device__ __forceinline__ void store_bf16x4(uint16_t* p, const float* f) {
-  uint2 v;
-  v.x = static_cast<uint32_t>(f2bf(f[0])) | (static_cast<uint32_t>(f2bf(f[1])) << 16);
-  v.y = static_cast<uint32_t>(f2bf(f[2])) | (static_cast<uint32_t>(f2bf(f[3])) << 16);
-  *reinterpret_cast<uint2*>(p) = v;
-}
-
-__device__ __forceinline__ void load4(const float* p, float* f) {
-  const float4 v = *reinterpret_cast<const float4*>(p);
-  f[0] = v.x;
-  f[1] = v.y;
-  f[2] = v.z;
-  f[3] = v.w;
-}
-
-__device__ __forceinline__ void store4(float* p, const float* f) {
-  *reinterpret_cast<float4*>(p) = make_float4(f[0], f[1], f[2], f[3]);
-}
-
-// An element whose bf16 compute copy no longer equals bf16(master) was overwritten behind the optimizer: it counts,
-// and is updated, with the copy's value (optim.hip sgd_kernel).
-__device__ __forceinline__ void resync4(float* wf, const uint16_t* w_bf16) {
-  const uint2 cv = *reinterpret_cast<const uint2*>(w_bf16);
-  const uint16_t cur[4] = {static_cast<uint16_t>(cv.x & 0xffffu), static_cast<uint16_t>(cv.x >> 16),
-                           static_cast<uint16_t>(cv.y & 0xffffu), static_cast<uint16_t>(cv.y >> 16)};
-#pragma unroll
-  for (int k = 0; k < 4; ++k)
-    if (cur[k] != f2bf(wf[k])) wf[k] = bf2f(cur[k]);
-}
 
 // The workgroup's (a, b) in a fixed order: lanes by butterfly, the four waves in wave order.
 __device__ __forceinline__ void store_pair(float a, float b, float2* out) {

@@ -8,7 +8,8 @@
 // kernel is HBM-bound by construction (27M params ~ 0.1 ms at 6 TB/s).
 //
 // Hyper-parameters live in a small device array `hp` (not kernel arguments) so
-// a captured HIP graph replays with the current learning rate / step.
+// a captured HIP graph replays with the current learning rate / step.  kind_update4 (optim_math.h) is the
+// one reader of these layouts:
 //   SGD  hp = [lr, momentum, weight_decay, grad_scale, nesterov, resync]
 //        resync != 0 (with a bf16 compute copy): an element whose compute copy no longer equals
 //        bf16(master) was overwritten outside the optimizer (load_state_dict, a Horovod
@@ -26,141 +27,6 @@ using namespace tony;
 namespace {
 
 constexpr int kThreads = 256;
-
-template <bool kGradBf16>
-__device__ __forceinline__ void load_grad4(const void* g, int64_t i, float* out) {
-  if constexpr (kGradBf16) {
-    const uint2 v = *reinterpret_cast<const uint2*>(static_cast<const uint16_t*>(g) + i);
-    out[0] = __uint_as_float(v.x << 16);
-    out[1] = __uint_as_float(v.x & 0xffff0000u);
-    out[2] = __uint_as_float(v.y << 16);
-    out[3] = __uint_as_float(v.y & 0xffff0000u);
-  } else {
-    const float4 v = *reinterpret_cast<const float4*>(static_cast<const float*>(g) + i);
-    out[0] = v.x;
-    out[1] = v.y;
-    out[2] = v.z;
-    out[3] = v.w;
-  }
-}
-
-__device__ __forceinline__ void store_bf16x4(uint16_t* p, const float* f) {
-  uint2 v;
-  v.x = static_cast<uint32_t>(f2bf(f[0])) | (static_cast<uint32_t>(f2bf(f[1])) << 16);
-  v.y = static_cast<uint32_t>(f2bf(f[2])) | (static_cast<uint32_t>(f2bf(f[3])) << 16);
-  *reinterpret_cast<uint2*>(p) = v;
-}
-
-template <bool kGradBf16>
-__global__ __launch_bounds__(kThreads) void sgd_kernel(float* __restrict__ w, float* __restrict__ v,
-                                                       const void* __restrict__ g,
-                                                       uint16_t* __restrict__ w_bf16, int64_t n4,
-                                                       const float* __restrict__ hp) {
-  const float lr = hp[0], mu = hp[1], wd = hp[2], gs = hp[3];
-  const bool nesterov = hp[4] != 0.f;
-  const bool resync = hp[5] != 0.f && w_bf16 != nullptr;
-  const int64_t stride = static_cast<int64_t>(gridDim.x) * kThreads;
-  for (int64_t q = static_cast<int64_t>(blockIdx.x) * kThreads + threadIdx.x; q < n4; q += stride) {
-    const int64_t i = q * 4;
-    float gf[4];
-    load_grad4<kGradBf16>(g, i, gf);
-    float4 wv = *reinterpret_cast<float4*>(w + i);
-    float4 vv = *reinterpret_cast<float4*>(v + i);
-    float wf[4] = {wv.x, wv.y, wv.z, wv.w};
-    float vf[4] = {vv.x, vv.y, vv.z, vv.w};
-    if (resync) {
-      const uint2 cv = *reinterpret_cast<const uint2*>(w_bf16 + i);
-      const uint16_t cur[4] = {static_cast<uint16_t>(cv.x & 0xffffu), static_cast<uint16_t>(cv.x >> 16),
-                               static_cast<uint16_t>(cv.y & 0xffffu), static_cast<uint16_t>(cv.y >> 16)};
-#pragma unroll
-      for (int k = 0; k < 4; ++k)
-        if (cur[k] != f2bf(wf[k])) wf[k] = bf2f(cur[k]);
-    }
-    sgd_update4(wf, vf, gf, lr, mu, wd, gs, nesterov);
-    *reinterpret_cast<float4*>(w + i) = make_float4(wf[0], wf[1], wf[2], wf[3]);
-    *reinterpret_cast<float4*>(v + i) = make_float4(vf[0], vf[1], vf[2], vf[3]);
-    if (w_bf16 != nullptr) store_bf16x4(w_bf16 + i, wf);
-  }
-}
-
-template <bool kGradBf16>
-__global__ __launch_bounds__(kThreads) void adam_kernel(float* __restrict__ w, float* __restrict__ m,
-                                                        float* __restrict__ v,
-                                                        const void* __restrict__ g,
-                                                        uint16_t* __restrict__ w_bf16, int64_t n4,
-                                                        const float* __restrict__ hp) {
-  const float lr = hp[0], b1 = hp[1], b2 = hp[2], eps = hp[3], wd = hp[4], gs = hp[5];
-  const float bc1 = hp[6], bc2 = hp[7];
-  const bool decoupled = hp[8] != 0.f;
-  const float step_size = lr / bc1;
-  const float inv_sqrt_bc2 = rsqrtf(bc2);
-  const int64_t stride = static_cast<int64_t>(gridDim.x) * kThreads;
-  for (int64_t q = static_cast<int64_t>(blockIdx.x) * kThreads + threadIdx.x; q < n4; q += stride) {
-    const int64_t i = q * 4;
-    float gf[4];
-    load_grad4<kGradBf16>(g, i, gf);
-    float4 wv = *reinterpret_cast<float4*>(w + i);
-    float4 mv = *reinterpret_cast<float4*>(m + i);
-    float4 vv = *reinterpret_cast<float4*>(v + i);
-    float wf[4] = {wv.x, wv.y, wv.z, wv.w};
-    float mf[4] = {mv.x, mv.y, mv.z, mv.w};
-    float vf[4] = {vv.x, vv.y, vv.z, vv.w};
-    adam_update4(wf, mf, vf, gf, lr, b1, b2, eps, wd, gs, step_size, inv_sqrt_bc2, decoupled);
-    *reinterpret_cast<float4*>(w + i) = make_float4(wf[0], wf[1], wf[2], wf[3]);
-    *reinterpret_cast<float4*>(m + i) = make_float4(mf[0], mf[1], mf[2], mf[3]);
-    *reinterpret_cast<float4*>(v + i) = make_float4(vf[0], vf[1], vf[2], vf[3]);
-    if (w_bf16 != nullptr) store_bf16x4(w_bf16 + i, wf);
-  }
-}
-
-template <bool kGradBf16>
-__global__ __launch_bounds__(kThreads) void adagrad_kernel(float* __restrict__ w, float* __restrict__ h,
-                                                           const void* __restrict__ g,
-                                                           uint16_t* __restrict__ w_bf16, int64_t n4,
-                                                           const float* __restrict__ hp) {
-  const float lr = hp[0], eps = hp[1], wd = hp[2], gs = hp[3];
-  const int64_t stride = static_cast<int64_t>(gridDim.x) * kThreads;
-  for (int64_t q = static_cast<int64_t>(blockIdx.x) * kThreads + threadIdx.x; q < n4; q += stride) {
-    const int64_t i = q * 4;
-    float gf[4];
-    load_grad4<kGradBf16>(g, i, gf);
-    float4 wv = *reinterpret_cast<float4*>(w + i);
-    float4 hv = *reinterpret_cast<float4*>(h + i);
-    float wf[4] = {wv.x, wv.y, wv.z, wv.w};
-    float hf[4] = {hv.x, hv.y, hv.z, hv.w};
-    adagrad_update4(wf, hf, gf, lr, eps, wd, gs);
-    *reinterpret_cast<float4*>(w + i) = make_float4(wf[0], wf[1], wf[2], wf[3]);
-    *reinterpret_cast<float4*>(h + i) = make_float4(hf[0], hf[1], hf[2], hf[3]);
-    if (w_bf16 != nullptr) store_bf16x4(w_bf16 + i, wf);
-  }
-}
-
-template <bool kGradBf16>
-__global__ __launch_bounds__(kThreads) void rmsprop_kernel(float* __restrict__ w, float* __restrict__ ms,
-                                                           float* __restrict__ mom,
-                                                           const void* __restrict__ g,
-                                                           uint16_t* __restrict__ w_bf16, int64_t n4,
-                                                           const float* __restrict__ hp) {
-  const float lr = hp[0], alpha = hp[1], mu = hp[2], eps = hp[3], wd = hp[4], gs = hp[5];
-  const bool tf_style = hp[6] != 0.f;
-  const int64_t stride = static_cast<int64_t>(gridDim.x) * kThreads;
-  for (int64_t q = static_cast<int64_t>(blockIdx.x) * kThreads + threadIdx.x; q < n4; q += stride) {
-    const int64_t i = q * 4;
-    float gf[4];
-    load_grad4<kGradBf16>(g, i, gf);
-    float4 wv = *reinterpret_cast<float4*>(w + i);
-    float4 sv = *reinterpret_cast<float4*>(ms + i);
-    float4 mv = *reinterpret_cast<float4*>(mom + i);
-    float wf[4] = {wv.x, wv.y, wv.z, wv.w};
-    float sf[4] = {sv.x, sv.y, sv.z, sv.w};
-    float mf[4] = {mv.x, mv.y, mv.z, mv.w};
-    rmsprop_update4(wf, sf, mf, gf, lr, alpha, mu, eps, wd, gs, tf_style);
-    *reinterpret_cast<float4*>(w + i) = make_float4(wf[0], wf[1], wf[2], wf[3]);
-    *reinterpret_cast<float4*>(ms + i) = make_float4(sf[0], sf[1], sf[2], sf[3]);
-    *reinterpret_cast<float4*>(mom + i) = make_float4(mf[0], mf[1], mf[2], mf[3]);
-    if (w_bf16 != nullptr) store_bf16x4(w_bf16 + i, wf);
-  }
-}
 
 // Sum of squares + non-finite flag over a flat bf16/fp32 gradient (H12):
 // out[0] += sum(g^2), out[1] = 1 if any element is inf/nan.
@@ -201,8 +67,8 @@ int grid_for(int64_t n4) {
 // -- global-norm clipping, non-finite step skip, EMA of the variables ------------------------------------
 // Three launches on one stream: grad_sumsq (one fp32 partial per workgroup of a FIXED grid, stored, so the
 // result does not depend on arrival order), clip_ctl (one workgroup folds the partials of every bucket into
-// ctl = [coef, skip, norm, skipped steps]) and apply_x (the update of `kind`, its gradient scale times coef,
-// nothing at all when skip is set, the EMA beside the master).
+// ctl = [coef, skip, norm, skipped steps]) and tony_optim_apply_x (optim_apply_kernel with kExt: the update of
+// `kind`, its gradient scale times coef, nothing at all when skip is set, the EMA beside the master).
 //   xhp = [clip_norm, base_grad_scale, skip_nonfinite, ema_decay, 1 - ema_decay]   (host-pushed, like hp)
 constexpr int kSumsqGrid = 1024;  // workgroups of every grad_sumsq launch = floats of one partial block
 
@@ -256,35 +122,27 @@ __global__ __launch_bounds__(kThreads) void clip_ctl_kernel(const float* __restr
   if (skip) ctl[3] += 1.f;
 }
 
-__device__ __forceinline__ void load4(const float* p, float* f) {
-  const float4 v = *reinterpret_cast<const float4*>(p);
-  f[0] = v.x;
-  f[1] = v.y;
-  f[2] = v.z;
-  f[3] = v.w;
-}
-
-__device__ __forceinline__ void store4(float* p, const float* f) {
-  *reinterpret_cast<float4*>(p) = make_float4(f[0], f[1], f[2], f[3]);
-}
-
-// kKind: 0 SGD (s0 = v), 1 Adam (m, v), 2 Adagrad (h), 3 RMSProp (ms, mom) -- the codes of plane_state().
-template <int kKind, bool kGradBf16>
-__global__ __launch_bounds__(kThreads) void apply_x_kernel(float* __restrict__ w, float* __restrict__ s0,
-                                                           float* __restrict__ s1, float* __restrict__ ema,
-                                                           const void* __restrict__ g,
-                                                           uint16_t* __restrict__ w_bf16, int64_t n4,
-                                                           const float* __restrict__ hp,
-                                                           const float* __restrict__ xhp,
-                                                           const float* __restrict__ ctl) {
-  float coef = 1.f;
-  if (ctl != nullptr) {
-    if (ctl[1] != 0.f) return;  // a skipped step touches nothing
-    coef = ctl[0];
+// The one apply kernel of the four kinds (OptKind, optim_math.h): s0 / s1 as kind_update4 takes them, s1 unused by
+// the one-state kinds.  kExt false is the plain step (ema, xhp, ctl unused); kExt true adds the clip coefficient
+// and the skip of ctl (nullptr: coef 1, no skip) and the EMA beside the master (nullptr: none).
+template <int kKind, bool kGradBf16, bool kExt>
+__global__ __launch_bounds__(kThreads) void optim_apply_kernel(float* __restrict__ w, float* __restrict__ s0,
+                                                               float* __restrict__ s1, float* __restrict__ ema,
+                                                               const void* __restrict__ g,
+                                                               uint16_t* __restrict__ w_bf16, int64_t n4,
+                                                               const float* __restrict__ hp,
+                                                               const float* __restrict__ xhp,
+                                                               const float* __restrict__ ctl) {
+  float coef = 1.f, omd = 0.f;
+  if constexpr (kExt) {
+    if (ctl != nullptr) {
+      if (ctl[1] != 0.f) return;  // a skipped step touches nothing
+      coef = ctl[0];
+    }
+    if (ema != nullptr) omd = xhp[4];
   }
-  const float omd = ema != nullptr ? xhp[4] : 0.f;
-  constexpr bool kTwo = kKind == 1 || kKind == 3;
-  const bool resync = kKind == 0 && hp[5] != 0.f && w_bf16 != nullptr;
+  constexpr bool kTwo = kKind == kAdam || kKind == kRMSProp;
+  const bool resync = kKind == kSGD && hp[5] != 0.f && w_bf16 != nullptr;
   const int64_t stride = static_cast<int64_t>(gridDim.x) * kThreads;
   for (int64_t q = static_cast<int64_t>(blockIdx.x) * kThreads + threadIdx.x; q < n4; q += stride) {
     const int64_t i = q * 4;
@@ -293,96 +151,60 @@ __global__ __launch_bounds__(kThreads) void apply_x_kernel(float* __restrict__ w
     load4(w + i, wf);
     load4(s0 + i, af);
     if constexpr (kTwo) load4(s1 + i, bf);
-    if constexpr (kKind == 0) {
-      if (resync) {
-        const uint2 cv = *reinterpret_cast<const uint2*>(w_bf16 + i);
-        const uint16_t cur[4] = {static_cast<uint16_t>(cv.x & 0xffffu), static_cast<uint16_t>(cv.x >> 16),
-                                 static_cast<uint16_t>(cv.y & 0xffffu), static_cast<uint16_t>(cv.y >> 16)};
-#pragma unroll
-        for (int k = 0; k < 4; ++k)
-          if (cur[k] != f2bf(wf[k])) wf[k] = bf2f(cur[k]);
-      }
-      sgd_update4(wf, af, gf, hp[0], hp[1], hp[2], hp[3] * coef, hp[4] != 0.f);
-    } else if constexpr (kKind == 1) {
-      const float lr = hp[0];
-      adam_update4(wf, af, bf, gf, lr, hp[1], hp[2], hp[3], hp[4], hp[5] * coef, lr / hp[6], rsqrtf(hp[7]),
-                   hp[8] != 0.f);
-    } else if constexpr (kKind == 2) {
-      adagrad_update4(wf, af, gf, hp[0], hp[1], hp[2], hp[3] * coef);
-    } else {
-      rmsprop_update4(wf, af, bf, gf, hp[0], hp[1], hp[2], hp[3], hp[4], hp[5] * coef, hp[6] != 0.f);
-    }
+    if (resync) resync4(wf, w_bf16 + i);
+    kind_update4<kKind, kExt>(wf, af, bf, gf, hp, coef);
     store4(w + i, wf);
     store4(s0 + i, af);
     if constexpr (kTwo) store4(s1 + i, bf);
-    if (ema != nullptr) {
-      float ef[4];
-      load4(ema + i, ef);
-      ema_update4(ef, wf, omd);
-      store4(ema + i, ef);
+    if constexpr (kExt) {
+      if (ema != nullptr) {
+        float ef[4];
+        load4(ema + i, ef);
+        ema_update4(ef, wf, omd);
+        store4(ema + i, ef);
+      }
     }
     if (w_bf16 != nullptr) store_bf16x4(w_bf16 + i, wf);
   }
 }
 
-template <int kKind>
-void launch_apply_x(float* w, float* s0, float* s1, float* ema, const void* g, int grad_bf16, uint16_t* w_bf16,
-                    int64_t n4, const float* hp, const float* xhp, const float* ctl, hipStream_t stream) {
+// n must be a multiple of 4 (flat buffers are padded by the caller).
+template <int kKind, bool kExt>
+int launch_apply(float* w, float* s0, float* s1, float* ema, const void* g, int grad_bf16, void* w_bf16, int64_t n,
+                 const float* hp, const float* xhp, const float* ctl, hipStream_t stream) {
+  if (n % 4) return -1;
+  const int64_t n4 = n / 4;
+  uint16_t* out = static_cast<uint16_t*>(w_bf16);
   if (grad_bf16)
-    apply_x_kernel<kKind, true><<<grid_for(n4), kThreads, 0, stream>>>(w, s0, s1, ema, g, w_bf16, n4, hp, xhp, ctl);
+    optim_apply_kernel<kKind, true, kExt><<<grid_for(n4), kThreads, 0, stream>>>(w, s0, s1, ema, g, out, n4, hp, xhp,
+                                                                                 ctl);
   else
-    apply_x_kernel<kKind, false><<<grid_for(n4), kThreads, 0, stream>>>(w, s0, s1, ema, g, w_bf16, n4, hp, xhp, ctl);
+    optim_apply_kernel<kKind, false, kExt><<<grid_for(n4), kThreads, 0, stream>>>(w, s0, s1, ema, g, out, n4, hp, xhp,
+                                                                                  ctl);
+  TONY_LAUNCH_CHECK();
+  return 0;
 }
 
 }  // namespace
 
-// n must be a multiple of 4 (flat buffers are padded by the caller).
 TONY_API int tony_sgd_step(float* w, float* v, const void* g, int grad_bf16, void* w_bf16, int64_t n,
                            const float* hp, hipStream_t stream) {
-  if (n % 4) return -1;
-  const int64_t n4 = n / 4;
-  if (grad_bf16)
-    sgd_kernel<true><<<grid_for(n4), kThreads, 0, stream>>>(w, v, g, static_cast<uint16_t*>(w_bf16), n4, hp);
-  else
-    sgd_kernel<false><<<grid_for(n4), kThreads, 0, stream>>>(w, v, g, static_cast<uint16_t*>(w_bf16), n4, hp);
-  TONY_LAUNCH_CHECK();
-  return 0;
+  return launch_apply<kSGD, false>(w, v, nullptr, nullptr, g, grad_bf16, w_bf16, n, hp, nullptr, nullptr, stream);
 }
 
 TONY_API int tony_adam_step(float* w, float* m, float* v, const void* g, int grad_bf16, void* w_bf16,
                             int64_t n, const float* hp, hipStream_t stream) {
-  if (n % 4) return -1;
-  const int64_t n4 = n / 4;
-  if (grad_bf16)
-    adam_kernel<true><<<grid_for(n4), kThreads, 0, stream>>>(w, m, v, g, static_cast<uint16_t*>(w_bf16), n4, hp);
-  else
-    adam_kernel<false><<<grid_for(n4), kThreads, 0, stream>>>(w, m, v, g, static_cast<uint16_t*>(w_bf16), n4, hp);
-  TONY_LAUNCH_CHECK();
-  return 0;
+  return launch_apply<kAdam, false>(w, m, v, nullptr, g, grad_bf16, w_bf16, n, hp, nullptr, nullptr, stream);
 }
 
 TONY_API int tony_adagrad_step(float* w, float* h, const void* g, int grad_bf16, void* w_bf16, int64_t n,
                                const float* hp, hipStream_t stream) {
-  if (n % 4) return -1;
-  const int64_t n4 = n / 4;
-  if (grad_bf16)
-    adagrad_kernel<true><<<grid_for(n4), kThreads, 0, stream>>>(w, h, g, static_cast<uint16_t*>(w_bf16), n4, hp);
-  else
-    adagrad_kernel<false><<<grid_for(n4), kThreads, 0, stream>>>(w, h, g, static_cast<uint16_t*>(w_bf16), n4, hp);
-  TONY_LAUNCH_CHECK();
-  return 0;
+  return launch_apply<kAdagrad, false>(w, h, nullptr, nullptr, g, grad_bf16, w_bf16, n, hp, nullptr, nullptr, stream);
 }
 
 TONY_API int tony_rmsprop_step(float* w, float* ms, float* mom, const void* g, int grad_bf16, void* w_bf16,
                                int64_t n, const float* hp, hipStream_t stream) {
-  if (n % 4) return -1;
-  const int64_t n4 = n / 4;
-  if (grad_bf16)
-    rmsprop_kernel<true><<<grid_for(n4), kThreads, 0, stream>>>(w, ms, mom, g, static_cast<uint16_t*>(w_bf16), n4, hp);
-  else
-    rmsprop_kernel<false><<<grid_for(n4), kThreads, 0, stream>>>(w, ms, mom, g, static_cast<uint16_t*>(w_bf16), n4, hp);
-  TONY_LAUNCH_CHECK();
-  return 0;
+  return launch_apply<kRMSProp, false>(w, ms, mom, nullptr, g, grad_bf16, w_bf16, n, hp, nullptr, nullptr, stream);
 }
 
 TONY_API int tony_grad_stats(const void* g, int grad_bf16, int64_t n, float* out, hipStream_t stream) {
@@ -430,18 +252,14 @@ TONY_API int tony_optim_apply_x(int kind, float* w, float* s0, float* s1, float*
                                 hipStream_t stream) {
   if (n % 4 || n < 0) return -1;
   if (ema != nullptr && xhp == nullptr) return -2;
-  if ((kind == 1 || kind == 3) && s1 == nullptr) return -3;
-  const int64_t n4 = n / 4;
-  uint16_t* out = static_cast<uint16_t*>(w_bf16);
+  if ((kind == kAdam || kind == kRMSProp) && s1 == nullptr) return -3;
   switch (kind) {
-    case 0: launch_apply_x<0>(w, s0, s1, ema, g, grad_bf16, out, n4, hp, xhp, ctl, stream); break;
-    case 1: launch_apply_x<1>(w, s0, s1, ema, g, grad_bf16, out, n4, hp, xhp, ctl, stream); break;
-    case 2: launch_apply_x<2>(w, s0, s1, ema, g, grad_bf16, out, n4, hp, xhp, ctl, stream); break;
-    case 3: launch_apply_x<3>(w, s0, s1, ema, g, grad_bf16, out, n4, hp, xhp, ctl, stream); break;
+    case kSGD: return launch_apply<kSGD, true>(w, s0, s1, ema, g, grad_bf16, w_bf16, n, hp, xhp, ctl, stream);
+    case kAdam: return launch_apply<kAdam, true>(w, s0, s1, ema, g, grad_bf16, w_bf16, n, hp, xhp, ctl, stream);
+    case kAdagrad: return launch_apply<kAdagrad, true>(w, s0, s1, ema, g, grad_bf16, w_bf16, n, hp, xhp, ctl, stream);
+    case kRMSProp: return launch_apply<kRMSProp, true>(w, s0, s1, ema, g, grad_bf16, w_bf16, n, hp, xhp, ctl, stream);
     default: return -4;
   }
-  TONY_LAUNCH_CHECK();
-  return 0;
 }
 
 // dst (bf16 or fp32) += src (fp32), n elements: folds an fp32 weight-gradient

@@ -163,18 +163,12 @@ __device__ __forceinline__ void update4(const ApplyArgs& a, int64_t i, const flo
   float wf[4] = {wv.x, wv.y, wv.z, wv.w};
   float4 mv = *reinterpret_cast<float4*>(a.s0 + i);
   float mf[4] = {mv.x, mv.y, mv.z, mv.w};
-  if constexpr (OPT == 0) {
-    sgd_update4(wf, mf, g, hp[0], hp[1], hp[2], hp[3], hp[4] != 0.f);
-  } else if constexpr (OPT == 2) {
-    adagrad_update4(wf, mf, g, hp[0], hp[1], hp[2], hp[3]);
+  if constexpr (OPT == kSGD || OPT == kAdagrad) {
+    kind_update4<OPT, false>(wf, mf, nullptr, g, hp, 1.f);
   } else {
     float4 vv = *reinterpret_cast<float4*>(a.s1 + i);
     float vf[4] = {vv.x, vv.y, vv.z, vv.w};
-    if constexpr (OPT == 1)
-      adam_update4(wf, mf, vf, g, hp[0], hp[1], hp[2], hp[3], hp[4], hp[5], hp[0] / hp[6], rsqrtf(hp[7]),
-                   hp[8] != 0.f);
-    else
-      rmsprop_update4(wf, mf, vf, g, hp[0], hp[1], hp[2], hp[3], hp[4], hp[5], hp[6] != 0.f);
+    kind_update4<OPT, false>(wf, mf, vf, g, hp, 1.f);
     *reinterpret_cast<float4*>(a.s1 + i) = make_float4(vf[0], vf[1], vf[2], vf[3]);
   }
   *reinterpret_cast<float4*>(a.master + i) = make_float4(wf[0], wf[1], wf[2], wf[3]);

@@ -1,4 +1,5 @@
-"""Fused optimizers over flat parameter shards (HIP kernels in csrc/optim.hip).
+"""Fused optimizers over flat parameter shards (HIP kernels in csrc/optim.hip: one apply kernel,
+``optim_apply_kernel``, instantiated per kind; the kinds' updates in csrc/optim_math.h).
 
 ``FlatSGD`` / ``FlatAdam`` / ``FlatAdagrad`` / ``FlatRMSProp`` / ``FlatLARS`` / ``FlatLAMB`` own an fp32 master
 copy of a flat parameter shard plus its optimizer state, consume a flat gradient (bf16 or fp32) and write the
@@ -20,7 +21,7 @@ from __future__ import annotations
 
 import bisect
 from dataclasses import dataclass
-from typing import List, Optional
+from typing import List, NamedTuple, Optional, Tuple
 
 import torch
 
@@ -35,6 +36,21 @@ N_XHP = 8            # xhp = [clip_norm, base_grad_scale, skip_nonfinite, ema_de
 def _f32(x: float) -> float:
     """``x`` rounded to fp32 (the CPU fallbacks form the clip coefficient in the kernels' precision)."""
     return torch.tensor(float(x), dtype=torch.float32).item()
+
+
+class _Kind(NamedTuple):
+    """What a flat optimizer class declares about its kind, once.
+
+    ``entry``  the plain entry point (``(w, *state, grad, grad_bf16, w_bf16, n, hp, stream)``); None: no plain form;
+    ``code``   the kind's number for ``tony_optim_apply_x`` and the PS data plane (csrc/optim_math.h ``OptKind``);
+               None: not available there;
+    ``state``  the ordered ``(checkpoint key, attribute)`` pairs of its state tensors, ``s0`` then ``s1``;
+    ``name``   the ``kind`` string of its checkpoints."""
+
+    entry: Optional[str]
+    code: Optional[int]
+    state: Tuple[Tuple[str, str], ...]
+    name: str
 
 
 class _FlatOptimizer:
@@ -54,6 +70,7 @@ class _FlatOptimizer:
     ``tony_optim_apply_x``, which reads the coefficient and the skip flag on the device."""
 
     n_hp = 0
+    kind: _Kind = None  # every concrete class declares its own
 
     def __init__(self, master: torch.Tensor, lr: float, weight_decay: float = 0.0, clip_norm=None,
                  skip_nonfinite: bool = False, ema_decay=None, ema_warmup: bool = False):
@@ -170,9 +187,9 @@ class _FlatOptimizer:
         """``apply_range`` with clipping / skip / EMA: tony_optim_apply_x, or the same on CPU tensors."""
         n = grad.numel()
         if self.w.is_cuda:
-            kind, s0, s1 = self.plane_state()
+            code, s0, s1 = self.plane_state()
             rc = _lib.lib().tony_optim_apply_x(
-                kind, self.w.data_ptr() + 4 * lo, s0.data_ptr() + 4 * lo, 0 if s1 is None else s1.data_ptr() + 4 * lo,
+                code, self.w.data_ptr() + 4 * lo, s0.data_ptr() + 4 * lo, 0 if s1 is None else s1.data_ptr() + 4 * lo,
                 0 if self.ema is None else self.ema.data_ptr() + 4 * lo, grad.data_ptr(),
                 int(grad.dtype == torch.bfloat16), _lib.ptr(out_bf16), n, self._hp_dev.data_ptr(),
                 self._xhp_dev.data_ptr(), self._ctl.data_ptr() if self.needs_norm else 0,
@@ -188,6 +205,9 @@ class _FlatOptimizer:
             self._apply_cpu(grad, lo, out_bf16)
         finally:
             self.grad_scale = gs
+        self._ema_cpu(lo, n)
+
+    def _ema_cpu(self, lo, n):
         if self.ema is not None:
             e = self.ema[lo:lo + n]
             e.add_((self.w[lo:lo + n] - e) * (1.0 - self._ema_decay_now()))
@@ -242,33 +262,71 @@ class _FlatOptimizer:
         if self.w.is_cuda:
             self._push_hp()
 
-    def apply_range(self, grad: torch.Tensor, lo: int = 0, out_bf16: torch.Tensor | None = None):
-        raise NotImplementedError
+    def _check_range(self, grad, lo):
+        n = grad.numel()
+        if lo < 0 or lo + n > self.w.numel() or lo % 4 or n % 4:
+            raise ValueError(f"range [{lo}, {lo + n}) outside the {self.w.numel()}-element shard or not 4-aligned")
+        return n
 
-    def step(self, grad: torch.Tensor, out_bf16: torch.Tensor | None = None):
-        """One whole-shard update: ``begin_step`` + ``apply_range`` over every element (with ``clip_norm`` or
-        ``skip_nonfinite``: the norm of ``grad`` first)."""
+    def _states(self):
+        return [getattr(self, attr) for _, attr in self.kind.state]
+
+    def apply_range(self, grad: torch.Tensor, lo: int = 0, out_bf16: torch.Tensor | None = None):
+        """Update master elements [lo, lo + grad.numel()) (one bucket of a sharded PS) with ``grad``;
+        hyper-parameters are those pushed by the last ``begin_step``."""
+        n = self._check_range(grad, lo)
+        if self._extended:
+            return self._apply_x(grad, lo, out_bf16)
+        if self.w.is_cuda:
+            entry = self.kind.entry
+            ptrs = [t.data_ptr() + 4 * lo for t in (self.w, *self._states())]
+            rc = getattr(_lib.lib(), entry)(*ptrs, grad.data_ptr(), int(grad.dtype == torch.bfloat16),
+                                            _lib.ptr(out_bf16), n, self._hp_dev.data_ptr(),
+                                            _lib.stream_ptr(self.w.device))
+            _lib.check(rc, entry)
+            return
+        self._apply_cpu(grad, lo, out_bf16)
+
+    def _begin_whole(self, grad: torch.Tensor):
+        """What every whole-shard ``step`` starts with: ``begin_step`` and, where it is needed, the norm of ``grad``."""
         if grad.numel() != self.w.numel():
             raise ValueError("grad / shard size mismatch")
         self.begin_step()
         if self.needs_norm:
             self.accumulate_sumsq(grad, 0)
             self.finish_norm(1)
+
+    def step(self, grad: torch.Tensor, out_bf16: torch.Tensor | None = None):
+        """One whole-shard update: ``begin_step`` + ``apply_range`` over every element (with ``clip_norm`` or
+        ``skip_nonfinite``: the norm of ``grad`` first)."""
+        self._begin_whole(grad)
         self.apply_range(grad, 0, out_bf16)
 
     def state_dict(self):
-        raise NotImplementedError
+        sd = {"kind": self.kind.name, "step": self.step_count}
+        sd.update((key, getattr(self, attr)) for key, attr in self.kind.state)
+        sd["lr"] = self.lr
+        return self._extras_state(sd)
+
+    def load_state_dict(self, sd):
+        self.step_count = int(sd["step"])
+        for key, attr in self.kind.state:
+            getattr(self, attr).copy_(sd[key])
+        self.lr = float(sd.get("lr", self.lr))
+        self._load_extras(sd)
 
     def plane_state(self):
         """``(opt, s0, s1)`` for the PS data plane's apply kernel (csrc/ps_plane.hip ``tony_ps_apply``): its
         optimizer code and the one or two state tensors it updates beside the master (``s1`` may be None)."""
-        raise NotImplementedError
+        s = self._states()
+        return self.kind.code, s[0], s[1] if len(s) > 1 else None
 
 
 class FlatSGD(_FlatOptimizer):
     """SGD with (Nesterov) momentum: v = mu*v + g + wd*w ; w -= lr*v (TF MomentumOptimizer semantics)."""
 
     n_hp = 6
+    kind = _Kind("tony_sgd_step", 0, (("momentum_buffer", "v"),), "sgd")
 
     def __init__(self, master, lr, momentum=0.9, weight_decay=0.0, nesterov=False, resync=False, **extra):
         super().__init__(master, lr, weight_decay, **extra)
@@ -276,29 +334,13 @@ class FlatSGD(_FlatOptimizer):
         self.nesterov = bool(nesterov)
         # resync: the bf16 compute copy (``out_bf16``) is the parameters users see and may overwrite
         # (load_state_dict, broadcast_parameters); elements changed there re-seed the fp32 master
-        # before the update (csrc/optim.hip sgd_kernel).  Off for the PS, whose masters are the truth.
+        # before the update (csrc/optim_math.h resync4).  Off for the PS, whose masters are the truth.
         self.resync = bool(resync)
         self.v = torch.zeros_like(master)
 
     def _hp_values(self):
         return [self.lr, self.momentum, self.weight_decay, self.grad_scale, 1.0 if self.nesterov else 0.0,
                 1.0 if self.resync else 0.0]
-
-    def apply_range(self, grad: torch.Tensor, lo: int = 0, out_bf16: torch.Tensor | None = None):
-        """Update master elements [lo, lo + grad.numel()) (one bucket of a sharded PS) with ``grad``;
-        hyper-parameters are those pushed by the last ``begin_step``."""
-        n = grad.numel()
-        if lo < 0 or lo + n > self.w.numel() or lo % 4 or n % 4:
-            raise ValueError(f"range [{lo}, {lo + n}) outside the {self.w.numel()}-element shard or not 4-aligned")
-        if self._extended:
-            return self._apply_x(grad, lo, out_bf16)
-        if self.w.is_cuda:
-            rc = _lib.lib().tony_sgd_step(self.w.data_ptr() + 4 * lo, self.v.data_ptr() + 4 * lo, grad.data_ptr(),
-                                          int(grad.dtype == torch.bfloat16), _lib.ptr(out_bf16), n,
-                                          self._hp_dev.data_ptr(), _lib.stream_ptr(self.w.device))
-            _lib.check(rc, "tony_sgd_step")
-            return
-        self._apply_cpu(grad, lo, out_bf16)
 
     def _apply_cpu(self, grad, lo, out_bf16):
         n = grad.numel()
@@ -313,23 +355,12 @@ class FlatSGD(_FlatOptimizer):
         if out_bf16 is not None:
             out_bf16.copy_(w)
 
-    def state_dict(self):
-        return self._extras_state({"kind": "sgd", "step": self.step_count, "momentum_buffer": self.v, "lr": self.lr})
-
-    def load_state_dict(self, sd):
-        self.step_count = int(sd["step"])
-        self.v.copy_(sd["momentum_buffer"])
-        self.lr = float(sd.get("lr", self.lr))
-        self._load_extras(sd)
-
-    def plane_state(self):
-        return 0, self.v, None
-
 
 class FlatAdam(_FlatOptimizer):
     """Adam / AdamW (``decoupled=True``) with bias correction."""
 
     n_hp = 9
+    kind = _Kind("tony_adam_step", 1, (("exp_avg", "m"), ("exp_avg_sq", "v")), "adam")
 
     def __init__(self, master, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, decoupled=False, **extra):
         super().__init__(master, lr, weight_decay, **extra)
@@ -343,21 +374,6 @@ class FlatAdam(_FlatOptimizer):
         t = self.step_count
         return [self.lr, self.b1, self.b2, self.eps, self.weight_decay, self.grad_scale,
                 1.0 - self.b1 ** t, 1.0 - self.b2 ** t, 1.0 if self.decoupled else 0.0]
-
-    def apply_range(self, grad: torch.Tensor, lo: int = 0, out_bf16: torch.Tensor | None = None):
-        n = grad.numel()
-        if lo < 0 or lo + n > self.w.numel() or lo % 4 or n % 4:
-            raise ValueError(f"range [{lo}, {lo + n}) outside the {self.w.numel()}-element shard or not 4-aligned")
-        if self._extended:
-            return self._apply_x(grad, lo, out_bf16)
-        if self.w.is_cuda:
-            rc = _lib.lib().tony_adam_step(self.w.data_ptr() + 4 * lo, self.m.data_ptr() + 4 * lo,
-                                           self.v.data_ptr() + 4 * lo, grad.data_ptr(),
-                                           int(grad.dtype == torch.bfloat16), _lib.ptr(out_bf16), n,
-                                           self._hp_dev.data_ptr(), _lib.stream_ptr(self.w.device))
-            _lib.check(rc, "tony_adam_step")
-            return
-        self._apply_cpu(grad, lo, out_bf16)
 
     def _apply_cpu(self, grad, lo, out_bf16):
         n = grad.numel()
@@ -375,26 +391,13 @@ class FlatAdam(_FlatOptimizer):
         if out_bf16 is not None:
             out_bf16.copy_(w)
 
-    def state_dict(self):
-        return self._extras_state({"kind": "adam", "step": self.step_count, "exp_avg": self.m, "exp_avg_sq": self.v,
-                                   "lr": self.lr})
-
-    def load_state_dict(self, sd):
-        self.step_count = int(sd["step"])
-        self.m.copy_(sd["exp_avg"])
-        self.v.copy_(sd["exp_avg_sq"])
-        self.lr = float(sd.get("lr", self.lr))
-        self._load_extras(sd)
-
-    def plane_state(self):
-        return 1, self.m, self.v
-
 
 class FlatAdagrad(_FlatOptimizer):
     """Adagrad: g' = g + wd*w ; h += g'^2 ; w -= lr*g' / (sqrt(h) + eps)  (``torch.optim.Adagrad`` with
     ``lr_decay=0``, Keras ``Adagrad``); ``h`` starts at ``initial_accumulator_value``."""
 
     n_hp = 4
+    kind = _Kind("tony_adagrad_step", 2, (("sum", "h"),), "adagrad")
 
     def __init__(self, master, lr, eps=1e-7, initial_accumulator_value=0.1, weight_decay=0.0, **extra):
         super().__init__(master, lr, weight_decay, **extra)
@@ -404,21 +407,6 @@ class FlatAdagrad(_FlatOptimizer):
     def _hp_values(self):
         return [self.lr, self.eps, self.weight_decay, self.grad_scale]
 
-    def apply_range(self, grad: torch.Tensor, lo: int = 0, out_bf16: torch.Tensor | None = None):
-        n = grad.numel()
-        if lo < 0 or lo + n > self.w.numel() or lo % 4 or n % 4:
-            raise ValueError(f"range [{lo}, {lo + n}) outside the {self.w.numel()}-element shard or not 4-aligned")
-        if self._extended:
-            return self._apply_x(grad, lo, out_bf16)
-        if self.w.is_cuda:
-            rc = _lib.lib().tony_adagrad_step(self.w.data_ptr() + 4 * lo, self.h.data_ptr() + 4 * lo,
-                                              grad.data_ptr(), int(grad.dtype == torch.bfloat16),
-                                              _lib.ptr(out_bf16), n, self._hp_dev.data_ptr(),
-                                              _lib.stream_ptr(self.w.device))
-            _lib.check(rc, "tony_adagrad_step")
-            return
-        self._apply_cpu(grad, lo, out_bf16)
-
     def _apply_cpu(self, grad, lo, out_bf16):
         n = grad.numel()
         w, h = self.w[lo:lo + n], self.h[lo:lo + n]
@@ -427,18 +415,6 @@ class FlatAdagrad(_FlatOptimizer):
         w.addcdiv_(g, h.sqrt().add_(self.eps), value=-self.lr)
         if out_bf16 is not None:
             out_bf16.copy_(w)
-
-    def state_dict(self):
-        return self._extras_state({"kind": "adagrad", "step": self.step_count, "sum": self.h, "lr": self.lr})
-
-    def load_state_dict(self, sd):
-        self.step_count = int(sd["step"])
-        self.h.copy_(sd["sum"])
-        self.lr = float(sd.get("lr", self.lr))
-        self._load_extras(sd)
-
-    def plane_state(self):
-        return 2, self.h, None
 
 
 class FlatRMSProp(_FlatOptimizer):
@@ -452,6 +428,7 @@ class FlatRMSProp(_FlatOptimizer):
     Both states are always kept; ``momentum=0`` falls out of the same formula."""
 
     n_hp = 7
+    kind = _Kind("tony_rmsprop_step", 3, (("square_avg", "ms"), ("momentum_buffer", "mom")), "rmsprop")
 
     def __init__(self, master, lr, alpha=0.9, momentum=0.0, eps=1e-8, weight_decay=0.0, tf_style=False, **extra):
         super().__init__(master, lr, weight_decay, **extra)
@@ -465,21 +442,6 @@ class FlatRMSProp(_FlatOptimizer):
     def _hp_values(self):
         return [self.lr, self.alpha, self.momentum, self.eps, self.weight_decay, self.grad_scale,
                 1.0 if self.tf_style else 0.0]
-
-    def apply_range(self, grad: torch.Tensor, lo: int = 0, out_bf16: torch.Tensor | None = None):
-        n = grad.numel()
-        if lo < 0 or lo + n > self.w.numel() or lo % 4 or n % 4:
-            raise ValueError(f"range [{lo}, {lo + n}) outside the {self.w.numel()}-element shard or not 4-aligned")
-        if self._extended:
-            return self._apply_x(grad, lo, out_bf16)
-        if self.w.is_cuda:
-            rc = _lib.lib().tony_rmsprop_step(self.w.data_ptr() + 4 * lo, self.ms.data_ptr() + 4 * lo,
-                                              self.mom.data_ptr() + 4 * lo, grad.data_ptr(),
-                                              int(grad.dtype == torch.bfloat16), _lib.ptr(out_bf16), n,
-                                              self._hp_dev.data_ptr(), _lib.stream_ptr(self.w.device))
-            _lib.check(rc, "tony_rmsprop_step")
-            return
-        self._apply_cpu(grad, lo, out_bf16)
 
     def _apply_cpu(self, grad, lo, out_bf16):
         n = grad.numel()
@@ -496,20 +458,12 @@ class FlatRMSProp(_FlatOptimizer):
             out_bf16.copy_(w)
 
     def state_dict(self):
-        return self._extras_state({"kind": "rmsprop", "step": self.step_count, "square_avg": self.ms,
-                                   "momentum_buffer": self.mom, "tf_style": self.tf_style, "lr": self.lr})
+        return {**super().state_dict(), "tf_style": self.tf_style}
 
     def load_state_dict(self, sd):
         if bool(sd.get("tf_style", self.tf_style)) != self.tf_style:
             raise ValueError(f"RMSProp checkpoint has tf_style={sd['tf_style']}, this optimizer {self.tf_style}")
-        self.step_count = int(sd["step"])
-        self.ms.copy_(sd["square_avg"])
-        self.mom.copy_(sd["momentum_buffer"])
-        self.lr = float(sd.get("lr", self.lr))
-        self._load_extras(sd)
-
-    def plane_state(self):
-        return 3, self.ms, self.mom
+        super().load_state_dict(sd)
 
 
 @dataclass
@@ -591,12 +545,6 @@ class _FlatLayerwise(_FlatOptimizer):
         self.table = torch.tensor([[1.0, 0.0]] * T, dtype=torch.float32, device=dev)
 
     # -- ranges -------------------------------------------------------------------------------------------
-    def _check_range(self, grad, lo):
-        n = grad.numel()
-        if lo < 0 or lo + n > self.w.numel() or lo % 4 or n % 4:
-            raise ValueError(f"range [{lo}, {lo + n}) outside the {self.w.numel()}-element shard or not 4-aligned")
-        return n
-
     def _item_range(self, lo: int, n: int):
         """Work items [i0, i1) that make up master elements [lo, lo + n)."""
         i0, i1 = bisect.bisect_left(self._item_lo, lo), bisect.bisect_left(self._item_lo, lo + n)
@@ -668,21 +616,11 @@ class _FlatLayerwise(_FlatOptimizer):
         return self.table[:, 0].clone()
 
     def step(self, grad: torch.Tensor, out_bf16: torch.Tensor | None = None):
-        if grad.numel() != self.w.numel():
-            raise ValueError("grad / shard size mismatch")
-        self.begin_step()
-        if self.needs_norm:
-            self.accumulate_sumsq(grad, 0)
-            self.finish_norm(1)
+        self._begin_whole(grad)
         self.norm_range(grad, 0, out_bf16)
         self.fold_norms()
         self.finish_ratios()
         self.apply_range(grad, 0, out_bf16)
-
-    def _ema_cpu(self, lo, n):
-        if self.ema is not None:
-            e = self.ema[lo:lo + n]
-            e.add_((self.w[lo:lo + n] - e) * (1.0 - self._ema_decay_now()))
 
     def plane_state(self):
         raise NotImplementedError("LARS and LAMB are not available on the xGMI PS data plane")
@@ -694,6 +632,7 @@ class FlatLARS(_FlatLayerwise):
     v = mu v + ratio (g + wd w) ; w -= lr v.  Tensors that are not adapted take ratio 1 and no weight decay."""
 
     n_hp = 8
+    kind = _Kind(None, None, (("momentum_buffer", "v"),), "lars")
     layer_kind = 0
 
     def __init__(self, master, lr, momentum=0.9, weight_decay=0.0, nesterov=False, trust_coef=0.001, eps=0.0,
@@ -765,16 +704,6 @@ class FlatLARS(_FlatLayerwise):
                 out.copy_(w)
         self._ema_cpu(lo, n)
 
-    def state_dict(self):
-        return self._extras_state({"kind": "lars", "step": self.step_count, "momentum_buffer": self.v,
-                                   "lr": self.lr})
-
-    def load_state_dict(self, sd):
-        self.step_count = int(sd["step"])
-        self.v.copy_(sd["momentum_buffer"])
-        self.lr = float(sd.get("lr", self.lr))
-        self._load_extras(sd)
-
 
 class FlatLAMB(_FlatLayerwise):
     """LAMB: Adam's moments with bias correction, u = (m/bc1) / (sqrt(v/bc2) + eps) + wd w, and per tensor
@@ -782,6 +711,7 @@ class FlatLAMB(_FlatLayerwise):
     and no weight decay (plain Adam)."""
 
     n_hp = 8
+    kind = _Kind(None, None, (("exp_avg", "m"), ("exp_avg_sq", "v")), "lamb")
     layer_kind = 1
 
     def __init__(self, master, lr=1e-3, betas=(0.9, 0.999), eps=1e-6, weight_decay=0.0,
@@ -852,17 +782,6 @@ class FlatLAMB(_FlatLayerwise):
             if out_bf16 is not None:
                 out_bf16[a - lo:b - lo].copy_(self.w[a:b])
         self._ema_cpu(lo, n)
-
-    def state_dict(self):
-        return self._extras_state({"kind": "lamb", "step": self.step_count, "exp_avg": self.m, "exp_avg_sq": self.v,
-                                   "lr": self.lr})
-
-    def load_state_dict(self, sd):
-        self.step_count = int(sd["step"])
-        self.m.copy_(sd["exp_avg"])
-        self.v.copy_(sd["exp_avg_sq"])
-        self.lr = float(sd.get("lr", self.lr))
-        self._load_extras(sd)
 
 
 def grad_stats(grad: torch.Tensor):

@@ -503,12 +503,9 @@ class _DistributedOptimizer:
                 opt.alpha, opt.momentum, opt.eps = float(g["alpha"]), float(g["momentum"]), float(g["eps"])
 
     def _state_tensors(self, opt) -> dict:
-        """torch's per-parameter state names of the wrapped Adam / Adagrad / RMSprop -> the flat state tensor."""
-        if self._kind == "adam":
-            return {"exp_avg": opt.m, "exp_avg_sq": opt.v}
-        if self._kind == "adagrad":
-            return {"sum": opt.h}
-        return {"square_avg": opt.ms, "momentum_buffer": opt.mom}
+        """torch's per-parameter state names of the wrapped Adam / Adagrad / RMSprop -> the flat state tensor (the
+        flat classes' checkpoint keys are torch's names)."""
+        return {key: getattr(opt, attr) for key, attr in opt.kind.state}
 
     # torch.optim.Optimizer surface
     @property

@@ -144,13 +144,19 @@ class ParameterServer:
         if self.layerwise:
             if optimizer.lower() == "lars":
                 opt_kw["trust_coef"] = trust_coef
-            self._refuse_plane_layerwise(model, mode, plane, device, group)  # before any tensor is made
+            self._refuse_plane(model, mode, plane, device, group,  # before any tensor is made
+                               "the lars and lamb optimizers are not available on the xGMI PS data plane: it applies "
+                               "chunk by chunk as the workers' rows land, before any tensor's norm exists; construct "
+                               "the ParameterServer with plane=\"rccl\"")
         self.needs_norm = clip_norm is not None or bool(skip_nonfinite)
         self.has_ema = ema_decay is not None
         if self.needs_norm or self.has_ema:
             opt_kw.update(clip_norm=clip_norm, skip_nonfinite=skip_nonfinite, ema_decay=ema_decay,
                           ema_warmup=ema_warmup)
-            self._refuse_plane_extras(model, mode, plane, device, group)  # before any tensor is made
+            self._refuse_plane(model, mode, plane, device, group,  # before any tensor is made
+                               "clip_norm, skip_nonfinite and ema_decay are not available on the xGMI PS data plane: "
+                               "it applies chunk by chunk as the workers' rows land, before a global norm exists, and "
+                               "keeps no EMA; construct the ParameterServer with plane=\"rccl\"")
         self.mode = mode
         self.sync = sync
         self.group = group
@@ -276,29 +282,15 @@ class ParameterServer:
 
     # -- helpers ---------------------------------------------------------------
     @staticmethod
-    def _refuse_plane_extras(model, mode, plane, device, group):
-        """clip_norm / skip_nonfinite / ema_decay on the xGMI data plane: refused before the plane (or any
-        tensor) is built.  An explicit ``plane="xgmi"`` is refused whatever the topology resolves it to."""
+    def _refuse_plane(model, mode, plane, device, group, message):
+        """What the xGMI data plane cannot do (``message``): refused before the plane (or any tensor) is built.
+        An explicit ``plane="xgmi"`` is refused whatever the topology resolves it to."""
         want = plane
         if plane == "auto" and mode == "dedicated" and coll.world(group) > 1:
             dev = torch.device(device) if device is not None else next(model.parameters()).device
             want = os.environ.get("TONY_PS_PLANE", "xgmi") if dev.type == "cuda" else "rccl"
         if want == "xgmi":
-            raise ValueError("clip_norm, skip_nonfinite and ema_decay are not available on the xGMI PS data plane: "
-                             "it applies chunk by chunk as the workers' rows land, before a global norm exists, and "
-                             "keeps no EMA; construct the ParameterServer with plane=\"rccl\"")
-
-    @staticmethod
-    def _refuse_plane_layerwise(model, mode, plane, device, group):
-        """optimizer="lars" / "lamb" on the xGMI data plane: refused like ``_refuse_plane_extras``."""
-        want = plane
-        if plane == "auto" and mode == "dedicated" and coll.world(group) > 1:
-            dev = torch.device(device) if device is not None else next(model.parameters()).device
-            want = os.environ.get("TONY_PS_PLANE", "xgmi") if dev.type == "cuda" else "rccl"
-        if want == "xgmi":
-            raise ValueError("the lars and lamb optimizers are not available on the xGMI PS data plane: it applies "
-                             "chunk by chunk as the workers' rows land, before any tensor's norm exists; construct "
-                             "the ParameterServer with plane=\"rccl\"")
+            raise ValueError(message)
 
     def _seg_kw(self, ranges) -> dict:
         """``segments=`` for a lars / lamb optimizer whose master is the flat ranges ``ranges`` laid end to end."""

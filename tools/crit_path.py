@@ -25,7 +25,8 @@ def main():
     # the host-ahead window: after the last long spin kernel
     start = max(spins, key=lambda i: rows[i][1] - rows[i][0]) + 1
     win = rows[start:]
-    ends = [r[1] for r in win if "sgd_kernel" in r[3]]
+    # the step's optimizer launch (sgd_kernel: traces from before the kinds shared one kernel)
+    ends = [r[1] for r in win if "optim_apply_kernel" in r[3] or "sgd_kernel" in r[3]]
     if len(ends) < 3:
         print("not enough steps after the spin kernel")
         return 1

@@ -29,7 +29,8 @@ def steps(path):
     out, cur = [], []
     for r in rows:
         cur.append(r)
-        if "sgd_kernel" in r[4] or "adam_kernel" in r[4]:
+        # a step ends at its optimizer launch (sgd_kernel / adam_kernel: traces from before the kinds shared one)
+        if "optim_apply_kernel" in r[4] or "sgd_kernel" in r[4] or "adam_kernel" in r[4]:
             out.append(cur)
             cur = []
     return out

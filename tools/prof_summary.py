@@ -7,8 +7,8 @@ usage: prof_summary.py <prof_dir> [--top N] [--skip W] [--by-grid]
 layer shapes launches different grids, so this separates e.g. the 35x35 from the 17x17 convs.
 
 Reads *kernel_trace.csv under <prof_dir> (rocprofv3 --kernel-trace --output-format csv).
-Every training step launches exactly one fused optimizer kernel (sgd_kernel /
-adam_kernel), so those launches delimit steps: kernels before the end of the W-th
+Every training step launches exactly one fused optimizer kernel (optim_apply_kernel;
+sgd_kernel / adam_kernel in traces from before the kinds shared one kernel), so those launches delimit steps: kernels before the end of the W-th
 optimizer launch (warmup, MIOpen solver search, first-call compiles) are dropped and
 the remaining window is reported per step, grouped into tony_amd HIP kernels vs
 MIOpen / hipBLASLt / PyTorch-native kernels.
@@ -17,6 +17,8 @@ import csv
 import glob
 import os
 import sys
+
+STEP_KERNELS = ("optim_apply_kernel", "sgd_kernel", "adam_kernel")  # the last two: older traces
 
 
 def classify(name):
@@ -36,7 +38,7 @@ def classify(name):
         return "tony HIP: in-place grad accumulate"
     if "box3_kernel" in n or "maxpool_" in n or "avgpool_" in n:
         return "tony HIP: pooling"
-    if "sgd_kernel" in n or "adam_kernel" in n or "grad_stats" in n or "grad_sumsq_kernel" in n \
+    if any(k in n for k in STEP_KERNELS) or "grad_stats" in n or "grad_sumsq_kernel" in n \
             or "clip_ctl_kernel" in n or "apply_x_kernel" in n:
         return "tony HIP: fused optimizer"
     if "xent" in n:
@@ -88,7 +90,7 @@ def main():
                     name = f"{short} grid={grid or r.get('Grid_Size', '?')}"
                 ks.append((int(col(r, "Start_Timestamp", "start")), int(col(r, "End_Timestamp", "end")), name))
     ks.sort()
-    opt_ends = [e for s, e, n in ks if "sgd_kernel" in n or "adam_kernel" in n]
+    opt_ends = [e for s, e, n in ks if any(k in n for k in STEP_KERNELS)]
     if len(opt_ends) <= skip:
         print(f"only {len(opt_ends)} optimizer launches, cannot skip {skip}")
         return 1
