@@ -5,10 +5,12 @@ Shard format: a directory of ``images_00000.npy`` (uint8 ``[n, H, W, 3]``, one `
 Nothing is decoded and nothing is downloaded.
 
 ``ImageBatches`` yields ``(x, y)``: ``x`` the channels_last ``[batch, 3, size, size]`` model input made by
-``ops.image.preprocess`` (random crop + flip for training, the 0.875 central crop for evaluation), ``y`` int64
+``ops.image.preprocess`` (random crop + flip for training, with ``colour="fast" | "full"`` followed by Inception's
+colour distortion from a per-sample table; the 0.875 central crop for evaluation, never distorted), ``y`` int64
 labels.  Batch ``t``'s sample indices and boxes are a pure function of ``(seed, rank, world, t)``: the epoch
 permutation comes from ``(seed, epoch)`` and is dealt to the ranks round-robin, the boxes from
-``(seed, rank, world, t)``, so ``seek(t)`` is all a resumed job needs and checkpoints do not change.
+``(seed, rank, world, t)``, the colour table from a stream of its own keyed ``(seed, rank, world, t, 1)``, so
+``seek(t)`` is all a resumed job needs and checkpoints do not change.
 
 A background thread gathers batch ``t+1`` from the memory-mapped shards into one of two staging slots (pinned on
 a GPU) while the step of batch ``t`` runs; on a GPU the slot and its box table go host-to-device on a copy stream
@@ -93,9 +95,13 @@ class _Shards:
 
 class ImageBatches:
     def __init__(self, directory: str, batch: int, size: int, train: bool = True, model: str = "inception",
-                 device="cpu", dtype=torch.float32, seed: int = 0, rank: int = 0, world: int = 1):
+                 device="cpu", dtype=torch.float32, seed: int = 0, rank: int = 0, world: int = 1,
+                 colour: str = "none"):
         if not 0 <= rank < world or batch < 1:
             raise ValueError(f"rank {rank} of {world}, batch {batch}")
+        if colour not in ("none", "fast", "full"):
+            raise ValueError(f"colour must be 'none', 'fast' or 'full', got {colour!r}")
+        self.colour = colour if train else "none"  # evaluation never distorts
         self.shards = _Shards(directory)
         self.batch, self.size, self.train, self.dtype = int(batch), int(size), bool(train), dtype
         self.device = torch.device(device)
@@ -124,10 +130,18 @@ class ImageBatches:
         self._stage_lab = [torch.zeros(batch, dtype=torch.int64, **pin) for _ in range(2)]
         self.x = torch.empty((batch, size, size, 3), dtype=dtype, device=self.device).permute(0, 3, 1, 2)
         self.y = torch.zeros(batch, dtype=torch.int64, device=self.device)
+        self._stage_col = self._dev_col = self._scratch = None
+        if self.colour != "none":  # the colour table travels as the boxes do
+            self._stage_col = [torch.zeros((batch, 5), dtype=torch.float32, **pin) for _ in range(2)]
         if on_gpu:
             self._dev = [torch.empty((batch, H, W, 3), dtype=torch.uint8, device=self.device) for _ in range(2)]
             self._dev_box = [torch.zeros((batch, 5), dtype=torch.int32, device=self.device) for _ in range(2)]
             self._dev_lab = [torch.zeros(batch, dtype=torch.int64, device=self.device) for _ in range(2)]
+            if self.colour != "none":
+                self._dev_col = [torch.zeros((batch, 5), dtype=torch.float32, device=self.device) for _ in range(2)]
+            if self.colour == "full":  # the contrast statistics of one launch
+                self._scratch = torch.empty(image.colour_scratch_floats(batch, size, size), dtype=torch.float32,
+                                            device=self.device)
             self._copy = torch.cuda.Stream(self.device)
             self._copied = [torch.cuda.Event() for _ in range(2)]  # slot k's host-to-device copy
             self._read = [None, None]  # slot k's device copy read by the preprocess launch
@@ -155,6 +169,14 @@ class ImageBatches:
         idx = self._perm[1][i * self.batch:(i + 1) * self.batch]
         rng = np.random.default_rng([self.seed, self.rank, self.world, int(t)])
         return idx, self._boxes(rng, len(idx), H, W)
+
+    def plan_colour(self, t: int) -> Optional[np.ndarray]:
+        """The colour table (``ops.image.inception_colour_params``) of batch ``t``, from an rng stream of its own:
+        a pure function of (seed, rank, world, t).  ``None`` without colour distortion."""
+        if self.colour == "none":
+            return None
+        rng = np.random.default_rng([self.seed, self.rank, self.world, int(t), 1])
+        return image.inception_colour_params(rng, self.batch, fast=self.colour == "fast")  # training batches are full
 
     # -- the filler thread ---------------------------------------------------------------------------------
 
@@ -201,6 +223,8 @@ class ImageBatches:
                 else:
                     self.shards.gather(dst[:m], idx)
                 self._stage_box[k].numpy()[:m] = boxes
+                if self.colour != "none":
+                    self._stage_col[k].numpy()[:m] = self.plan_colour(t)
                 self._stage_lab[k].numpy()[:m] = self.shards.labels[idx]
                 self.fill_ms += (time.perf_counter() - f0) * 1e3
                 self.filled += 1
@@ -227,6 +251,8 @@ class ImageBatches:
                     self._copy.wait_event(self._read[k])  # the launch that read the slot's previous batch
                 self._dev[k][:m].copy_(self._stage[k][:m], non_blocking=True)
                 self._dev_box[k][:m].copy_(self._stage_box[k][:m], non_blocking=True)
+                if self.colour != "none":
+                    self._dev_col[k][:m].copy_(self._stage_col[k][:m], non_blocking=True)
                 self._dev_lab[k][:m].copy_(self._stage_lab[k][:m], non_blocking=True)
                 self._copied[k].record(self._copy)
             self._free.put((k, self._copied[k]))  # the filler refills the slot once the copy has read it
@@ -247,20 +273,26 @@ class ImageBatches:
             cur = torch.cuda.current_stream(self.device)
             cur.wait_event(self._copied[k])
             image.preprocess(self._dev[k][:m], self._dev_box[k][:m], self.size, self.dtype, self.scale, self.bias,
-                             out=x)
+                             out=x, **self._colour_args(self._dev_col, k, m))
             y.copy_(self._dev_lab[k][:m], non_blocking=True)
             if self._read[k] is None:
                 self._read[k] = torch.cuda.Event()
             self._read[k].record(cur)
         else:
             image.preprocess(self._stage[k][:m], self._stage_box[k][:m], self.size, self.dtype, self.scale,
-                             self.bias, out=x)
+                             self.bias, out=x, **self._colour_args(self._stage_col, k, m))
             y.copy_(self._stage_lab[k][:m])
             self._free.put((k, None))
         self._pending = None
         self.t = t + 1
         self._stage_next()  # batch t+1's copy overlaps the step of batch t
         return x, y
+
+    def _colour_args(self, slots, k: int, m: int) -> dict:
+        """``preprocess``'s colour arguments for slot ``k``: none at all without colour distortion."""
+        if self.colour == "none":
+            return {}
+        return dict(colour=slots[k][:m], colour_has_contrast=self.colour == "full", scratch=self._scratch)
 
     def __iter__(self):
         """One epoch of this rank from batch 0."""

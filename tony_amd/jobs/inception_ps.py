@@ -81,10 +81,16 @@ def main(argv=None) -> int:
     ap.add_argument("--data-dir", default=None,
                     help="train from the uint8 shards in DIR (tony_amd/data/images.py: random crop, flip, resize on "
                          "the GPU) instead of one synthetic batch")
+    ap.add_argument("--colour", default="none", choices=["none", "fast", "full"],
+                    help="with --data-dir: the recipe's colour distortion after the crop (fast: brightness and "
+                         "saturation; full: brightness, saturation, hue and contrast in one of four random orders), "
+                         "clipped to [0, 1] (none: off)")
     ap.add_argument("--eval-dir", default=None,
                     help="after training, top-1 / top-5 over the shards in DIR (central crop, eval mode, the EMA "
                          "weights when --ema-decay is set)")
     a = ap.parse_args(argv)
+    if a.colour != "none" and not a.data_dir:
+        ap.error("--colour distorts the images of --data-dir: give --data-dir")
     tc = TFConfig.from_env()
     on_gpu = torch.cuda.is_available()
     mode = a.ps_mode
@@ -212,7 +218,7 @@ def main(argv=None) -> int:
         from tony_amd.data.images import ImageBatches
 
         batches = ImageBatches(a.data_dir, a.batch_size, a.image_size, train=True, model="inception", device=dev,
-                               dtype=dtype, seed=0, rank=data_rank, world=data_world)
+                               dtype=dtype, seed=0, rank=data_rank, world=data_world, colour=a.colour)
         batches.seek(start)  # batch t is a pure function of t: a resumed gang continues where it was
         wait0 = 0.0
     else:
@@ -285,7 +291,7 @@ def main(argv=None) -> int:
         metric(model="inception_v3", images_per_sec=float(rate), workers=workers, ps_mode=mode, loss=float(loss),
                dtype="fp32" if dtype == torch.float32 else "bf16", x3=x3, sync=ps.sync,
                start_step=start, steps=total, plane=_plane_name(ps), verified=coll.data_plane_status(),
-               collective_fallbacks=coll.fallback_count(), **extra)
+               collective_fallbacks=coll.fallback_count(), colour=a.colour, **extra)
     log(f"{float(rate):.1f} images/sec total over {workers} workers ({mode} PS)")
     dist.barrier()
     # orderly shutdown: drain the device (side streams included) and tear the process group down before

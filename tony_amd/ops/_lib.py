@@ -113,6 +113,11 @@ _SIGNATURES = {
     # image input pipeline (csrc/image.hip, ops/image.py) and top-k evaluation counters (csrc/metrics.hip)
     "tony_image_preprocess": [c_void_p, c_int, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_float,
                               c_float, c_float, c_float, c_float, c_float, c_void_p],
+    # ... with the per-sample colour distortion table: the scratch size, and statistics + apply
+    "tony_image_colour_scratch_floats": [c_int, c_int, c_int],
+    "tony_image_preprocess_colour": [c_void_p, c_int, c_void_p, c_void_p, c_int, c_void_p, c_int64, c_void_p, c_int,
+                                     c_int, c_int, c_int, c_int, c_int, c_float, c_float, c_float, c_float, c_float,
+                                     c_float, c_void_p],
     "tony_topk_count": [c_void_p, c_int, c_int64, c_int, c_int64, c_void_p, c_int, c_void_p, c_void_p],
     "tony_dropout_fwd": [c_void_p, c_void_p, c_void_p, c_int64, c_int, c_float, c_void_p, c_void_p],
     "tony_dropout_bwd": [c_void_p, c_void_p, c_void_p, c_int64, c_int, c_float, c_void_p],

@@ -7,7 +7,10 @@ arms take turns window by window so drift hits both alike.
     python tools/image_bench.py [--batch 128] [--src 346] [--size 299] [--launches 20] [--rounds 5]
 
 Prints per arm and dtype the median / min / max us per batch over the rounds, and for the kernel the GB/s its
-bytes imply: the source bytes inside the boxes plus the output bytes.
+bytes imply: the source bytes inside the boxes plus the output bytes.  The colour-distortion forms of the kernel
+(``preprocess(..., colour=table)``) take their turns in the same rounds: the fast form (brightness and saturation:
+one launch), the full form (statistics + fold + apply) and the full form's apply pass alone (the same table with
+the statistics skipped); the statistics pass is listed as the difference of the two medians.
 """
 import argparse
 import os
@@ -29,7 +32,8 @@ def main():
     ap.add_argument("--launches", type=int, default=20)
     ap.add_argument("--rounds", type=int, default=5)
     a = ap.parse_args()
-    from tony_amd.ops.image import inception_train_boxes, normalisation, preprocess
+    from tony_amd.ops.image import (colour_scratch_floats, inception_colour_params, inception_train_boxes,
+                                    normalisation, preprocess)
 
     dev = torch.device("cuda", 0)
     N, S, O = a.batch, a.src, a.size
@@ -45,6 +49,16 @@ def main():
     def kernel(dtype):
         out = torch.empty((N, O, O, 3), dtype=dtype, device=dev).permute(0, 3, 1, 2)
         return lambda: preprocess(src, boxes, O, dtype, scale, bias, out=out)
+
+    crng = np.random.default_rng(1)
+    fast = torch.from_numpy(inception_colour_params(crng, N, fast=True)).to(dev)
+    full = torch.from_numpy(inception_colour_params(crng, N)).to(dev)
+    scratch = torch.empty(colour_scratch_floats(N, O, O), dtype=torch.float32, device=dev)
+
+    def coloured(dtype, table, stats):
+        out = torch.empty((N, O, O, 3), dtype=dtype, device=dev).permute(0, 3, 1, 2)
+        return lambda: preprocess(src, boxes, O, dtype, scale, bias, out=out, colour=table,
+                                  colour_has_contrast=stats, scratch=scratch if stats else None)
 
     def composed(dtype):
         out = torch.empty((N, O, O, 3), dtype=dtype, device=dev).permute(0, 3, 1, 2)
@@ -63,6 +77,9 @@ def main():
     for name, dtype in (("bf16", torch.bfloat16), ("fp32", torch.float32)):
         esz = 2 if dtype == torch.bfloat16 else 4
         variants.append((f"tony_image_preprocess {name}", box_bytes + N * O * O * 3 * esz, kernel(dtype)))
+        variants.append((f"colour fast           {name}", 0, coloured(dtype, fast, False)))
+        variants.append((f"colour full           {name}", 0, coloured(dtype, full, True)))
+        variants.append((f"colour full, apply    {name}", 0, coloured(dtype, full, False)))
         variants.append((f"torch composition     {name}", 0, composed(dtype)))
     for _, _, fn in variants:  # warm up: code objects loaded, clocks up
         for _ in range(3):
@@ -85,6 +102,9 @@ def main():
         med = statistics.median(v)
         rate = f"{nbytes / med / 1e3:8.1f} GB/s" if nbytes else ""
         print(f"{name:30s} {med:10.1f} us  (min {min(v):.1f}, max {max(v):.1f})  {rate}")
+        if name.startswith("colour full, apply"):
+            stats = statistics.median(us[name.replace("full, apply", "full       ")]) - med
+            print(f"{name.replace('full, apply', 'full, stats'):30s} {stats:10.1f} us  (full - apply)")
 
 
 if __name__ == "__main__":
