@@ -33,6 +33,8 @@ def main(argv=None) -> int:
     ap.add_argument("--batch-size", type=int, default=1024)
     ap.add_argument("--epochs", type=int, default=2)
     ap.add_argument("--lr", type=float, default=0.1)
+    ap.add_argument("--gradient-compression", choices=["none", "2bit"], default="none")
+    ap.add_argument("--gc-threshold", type=float, default=0.5)
     a = ap.parse_args(argv)
     if kv.run_role():  # scheduler / server: serve until the workers are done
         return 0
@@ -47,6 +49,8 @@ def main(argv=None) -> int:
     store.init("fc_weight", w)
     store.init("fc_bias", b)
     store.set_optimizer(kv.create_optimizer("sgd", learning_rate=a.lr, rescale_grad=1.0 / (a.batch_size * nw)))
+    if a.gradient_compression != "none":  # (the default takes none of the compression code)
+        store.set_gradient_compression({"type": a.gradient_compression, "threshold": a.gc_threshold})
     mse = None
     for epoch in range(a.epochs):
         for lo in range(0, xs.shape[0], a.batch_size):

@@ -221,6 +221,11 @@ _SIGNATURES = {
     # parameter-server data plane over xGMI windows (csrc/ps_plane.hip, parallel/ps_plane.py)
     "tony_ps_header_bytes": [],
     "tony_kv_copy": [c_void_p, c_void_p, c_int64, c_void_p, c_void_p],
+    # 2-bit gradient compression of the kvstore (words, grad, residual, n, thr, flag | dst, words, n, thr, nsrc,
+    # stride, window)
+    "tony_kv_quant_blocks": [c_int64],
+    "tony_kv_quant2": [c_void_p, c_void_p, c_void_p, c_int64, c_float, c_void_p, c_void_p],
+    "tony_kv_dequant2": [c_void_p, c_void_p, c_int64, c_float, c_int, c_int64, c_void_p, c_void_p],
     "tony_ps_max_buckets": [],
     "tony_ps_max_blocks": [],
     "tony_ps_land_entry_bytes": [],

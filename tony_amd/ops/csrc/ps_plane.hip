@@ -561,3 +561,154 @@ TONY_API int tony_ps_error(void* window, int* err) {
   if (e == hipSuccess && *err != 0) e = hipMemset(word, 0, sizeof(int));
   return static_cast<int>(e);
 }
+
+// ------------------------------------------------------------- kvstore 2-bit gradient compression --
+// set_gradient_compression({'type': '2bit', 'threshold': thr}) of parallel/kvstore.py: a worker keeps an fp32
+// residual r per key; a push of g sends, per element, t = r + g as one of three codes -- 1 (t >= thr, the
+// receiver adds +thr, r = t - thr), 2 (t <= -thr: -thr, r = t + thr) or 0 (nothing, r = t; a NaN t compares
+// false twice) -- every line one fp32 operation.  Element i is bits 2*(i&15), 2*(i&15)+1 of u32 word i>>4;
+// the unused pairs of the last word are 0; code 3 is never produced and decodes to 0.
+namespace {
+
+constexpr int kQuantTile = 1024;  // elements of one wave's step: 4 rows of 64 lanes x float4 = 64 words
+
+__device__ __forceinline__ uint32_t quant1(float g, float& r, float thr) {
+  const float t = r + g;
+  uint32_t code = 0;
+  float nr = t;
+  if (t >= thr) {
+    code = 1;
+    nr = t - thr;
+  } else if (t <= -thr) {
+    code = 2;
+    nr = t + thr;
+  }
+  r = nr;
+  return code;
+}
+
+// One pass, 12.25 B per element.  A wave takes tiles of 1024 elements as four rows of 256: in row j lane l
+// loads the float4 of grad and residual at element 256 j + 4 l (16-B accesses, contiguous across the wave)
+// and writes the residual back the same way.  Its four codes are 8 bits of a word that the lane's quad
+// (16 elements) shares; the quad's lanes exchange their four rows' bytes, lane q*4+j assembles word (j, q),
+// and one more permute hands word 16 j + q to lane 16 j + q: the wave stores its 64 words as one contiguous
+// 256-B row (no 4-B stores at a 16-B stride into a peer's window, no word written twice).  Elements at or
+// past n are neither read nor written and code 0; words at or past ceil(n / 16) are not written.
+// flag (nullable): the hand-off of kv_copy_flag_kernel -- every workgroup adds 1 after its bytes.
+__global__ __launch_bounds__(256) void kv_quant2_kernel(const float* __restrict__ grad, float* __restrict__ res,
+                                                        uint32_t* __restrict__ words, int64_t n, float thr,
+                                                        uint32_t* flag) {
+  const int lane = threadIdx.x & 63;
+  const int64_t ntiles = (n + kQuantTile - 1) / kQuantTile, nwords = (n + 15) >> 4;
+  const int64_t wave = static_cast<int64_t>(blockIdx.x) * 4 + (threadIdx.x >> 6);
+  for (int64_t tile = wave; tile < ntiles; tile += static_cast<int64_t>(gridDim.x) * 4) {  // (wave-uniform)
+    uint32_t bytes = 0;  // byte j: this lane's four codes of row j
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      const int64_t e = tile * kQuantTile + j * 256 + lane * 4;
+      uint32_t b = 0;
+      if (e + 4 <= n) {
+        const float4 g = *reinterpret_cast<const float4*>(grad + e);
+        float4 r = *reinterpret_cast<const float4*>(res + e);
+        b = quant1(g.x, r.x, thr) | (quant1(g.y, r.y, thr) << 2) | (quant1(g.z, r.z, thr) << 4) |
+            (quant1(g.w, r.w, thr) << 6);
+        *reinterpret_cast<float4*>(res + e) = r;
+      } else {
+        for (int k = 0; k < 4 && e + k < n; ++k) {
+          float r = res[e + k];
+          b |= quant1(grad[e + k], r, thr) << (2 * k);
+          res[e + k] = r;
+        }
+      }
+      bytes |= b << (8 * j);
+    }
+    const int j = lane & 3;
+    uint32_t word = 0;  // word (row j, quad lane >> 2): byte j of the quad's four lanes, in lane order
+#pragma unroll
+    for (int k = 0; k < 4; ++k) word |= ((__shfl(bytes, (lane & ~3) | k) >> (8 * j)) & 0xffu) << (8 * k);
+    // word 16 j + q of the tile sits in lane 4 q + j: bring it to lane 16 j + q
+    word = __shfl(word, 4 * (lane & 15) + (lane >> 4));
+    const int64_t wi = tile * (kQuantTile / 16) + lane;
+    if (wi < nwords) words[wi] = word;
+  }
+  if (flag != nullptr) {
+    __threadfence_system();  // this workgroup's words are visible to the consumer before its add
+    __syncthreads();
+    if (threadIdx.x == 0) __hip_atomic_fetch_add(flag, 1u, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
+  }
+}
+
+__device__ __forceinline__ float decode2(uint32_t word, int k, float thr) {
+  const uint32_t c = (word >> (2 * k)) & 3u;
+  return c == 1u ? thr : (c == 2u ? -thr : 0.0f);
+}
+
+// dst[i] = v_0[i]; += v_1[i]; ... over the nsrc packed sources (the order a server merges a round in), 4
+// elements and one 16-B store per lane (a quad shares its word's 4-B load): 4.25 B per element at nsrc = 1.
+// err (nullable): see kv_copy_kernel.
+__global__ __launch_bounds__(256) void kv_dequant2_kernel(const uint32_t* __restrict__ words, float* __restrict__ dst,
+                                                          int64_t n, float thr, int nsrc, int64_t stride,
+                                                          const int* err) {
+  if (err != nullptr && __hip_atomic_load(err, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM) != 0) return;
+  const int64_t n4 = (n + 3) >> 2;
+  for (int64_t i = static_cast<int64_t>(blockIdx.x) * 256 + threadIdx.x; i < n4;
+       i += static_cast<int64_t>(gridDim.x) * 256) {
+    const int64_t e = i * 4;
+    const int k0 = static_cast<int>(e & 15);
+    float acc[4];
+    for (int s = 0; s < nsrc; ++s) {
+      const uint32_t w = words[s * stride + (e >> 4)];
+#pragma unroll
+      for (int k = 0; k < 4; ++k) {
+        const float v = decode2(w, k0 + k, thr);
+        acc[k] = s == 0 ? v : acc[k] + v;
+      }
+    }
+    if (e + 4 <= n) {
+      *reinterpret_cast<float4*>(dst + e) = make_float4(acc[0], acc[1], acc[2], acc[3]);
+    } else {
+      for (int k = 0; k < 4 && e + k < n; ++k) dst[e + k] = acc[k];
+    }
+  }
+}
+
+int kv_quant_blocks(int64_t n) {
+  return static_cast<int>(std::min<int64_t>(1024, (n + 4 * kQuantTile - 1) / (4 * kQuantTile)));
+}
+
+}  // namespace
+
+// workgroups of one tony_kv_quant2 launch over n elements (what a compressed push adds to the consumer's flag)
+TONY_API int tony_kv_quant_blocks(int64_t n) { return n <= 0 ? 0 : kv_quant_blocks(n); }
+
+// residual <- quantisation error of residual + grad, dst_words <- the ceil(n / 16) packed codes (local memory
+// or a mapped peer window); flag (nullable): one add per workgroup, tony_kv_quant_blocks(n) in all
+TONY_API int tony_kv_quant2(void* dst_words, const float* grad, float* residual, int64_t n, float thr, void* flag,
+                            hipStream_t stream) {
+  if (dst_words == nullptr || grad == nullptr || residual == nullptr || n <= 0 || !(thr > 0.f) ||
+      (reinterpret_cast<uintptr_t>(grad) & 15) || (reinterpret_cast<uintptr_t>(residual) & 15) ||
+      (reinterpret_cast<uintptr_t>(dst_words) & 3) || (reinterpret_cast<uintptr_t>(flag) & 3))
+    return -1;
+  kv_quant2_kernel<<<kv_quant_blocks(n), 256, 0, stream>>>(grad, residual, static_cast<uint32_t*>(dst_words), n, thr,
+                                                           static_cast<uint32_t*>(flag));
+  TONY_LAUNCH_CHECK();
+  return 0;
+}
+
+// dst[0, n) <- the ordered sum over nsrc packed sources, source s at words + s * src_stride_words; window
+// (nullable): write nothing when that window's error word is set (a timed-out wait ahead of it)
+TONY_API int tony_kv_dequant2(float* dst, const uint32_t* words, int64_t n, float thr, int nsrc,
+                              int64_t src_stride_words, void* window, hipStream_t stream) {
+  if (dst == nullptr || words == nullptr || n < 0 || !(thr > 0.f) || nsrc < 1 ||
+      (nsrc > 1 && src_stride_words < (n + 15) / 16) || (reinterpret_cast<uintptr_t>(dst) & 15) ||
+      (reinterpret_cast<uintptr_t>(words) & 3))
+    return -1;
+  if (n == 0) return 0;
+  const int64_t n4 = (n + 3) >> 2;
+  const int blocks = static_cast<int>(std::min<int64_t>(1024, (n4 + 255) / 256));
+  kv_dequant2_kernel<<<blocks, 256, 0, stream>>>(
+      words, dst, n, thr, nsrc, src_stride_words,
+      window == nullptr ? nullptr : reinterpret_cast<const int*>(static_cast<const uint8_t*>(window) + kErrOff));
+  TONY_LAUNCH_CHECK();
+  return 0;
+}

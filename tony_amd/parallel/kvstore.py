@@ -42,6 +42,22 @@ tensors, keep the gloo payload.  A worker re-pushing a key before pulling it (it
 been read yet) sends that push over gloo: the pull's reply is what orders the server's read of the row
 before the worker's next store into it (the server reads the row on its stream before it stores the
 reply; the worker's next push is issued behind its wait for that reply).
+
+Gradient compression (``set_gradient_compression({'type': '2bit', 'threshold': thr})``, the dist modes): every
+worker keeps an fp32 residual ``r`` per fp32 key on the gradient's device, zero before the first compressed push.
+A push of ``g`` (a list summed first) forms ``t = r + g`` and sends one of three codes per element: 1 when
+``t >= thr`` (``r = t - thr``), 2 when ``t <= -thr`` (``r = t + thr``), else 0 (``r = t``; a NaN ``t`` compares
+false twice) -- each line one fp32 operation.  Element ``i`` is bits ``2 * (i & 15)`` and the next of
+little-endian u32 word ``i >> 4``; a push carries ``ceil(n / 16)`` words, the unused pairs of the last one 0.
+The receiver decodes 0 / 1 / 2 to ``0.0`` / ``+thr`` / ``-thr`` (code 3, never produced, to ``0.0``) and merges
+the fp32 values as it merges plain pushes, so the optimizer sees the sum of the decoded pushes; pulls are never
+compressed and keys of another dtype are pushed as without it.  On the plane one kernel quantises, updates the
+residual and stores the words straight into the worker's row of the server's window (``tony_kv_quant2``, counted
+on the key's push flag by ``tony_kv_quant_blocks(n)`` workgroups: 0.25 B per element cross the link in place of
+4), and the server's read of the row decodes it (``tony_kv_dequant2``); a push that keeps the gloo payload sends
+the words.  ``dist_device_sync`` all-gathers the words and every worker sums the decoded pushes in rank order.
+The call is collective over the workers like ``set_optimizer`` (rank 0 ships the setting to the servers) and is
+allowed until the first push; a store that never gets it takes none of this code.
 """
 from __future__ import annotations
 
@@ -55,6 +71,9 @@ import torch
 import torch.distributed as dist
 
 OP_INIT, OP_PUSH, OP_PULL, OP_OPT, OP_STOP, OP_PUSH_X, OP_PULL_X = range(7)  # _X: payload on the GPU plane
+# gradient compression: the setting (JSON, like OP_OPT), a 2-bit push with its words over gloo (the header keeps
+# the gradient's numel; the payload is ceil(numel / 16) int32 words) and one with its words on the GPU plane
+OP_GC, OP_PUSH_C, OP_PUSH_CX = 7, 8, 9
 TAG_HDR, TAG_DATA, TAG_REPLY = 1, 2, 3
 _DTYPES = [torch.float32, torch.float16, torch.bfloat16, torch.float64, torch.int64, torch.int32, torch.uint8]
 _EXIT_KEY = "tony/kv/exited"
@@ -133,6 +152,107 @@ def _merge(vals: List[torch.Tensor]) -> torch.Tensor:
     return out
 
 
+# -- 2-bit gradient compression (module docstring) ----------------------------------------------
+def _gc_threshold(params) -> Optional[float]:
+    """The threshold a ``set_gradient_compression`` request asks 2-bit compression for; None for no compression."""
+    if not isinstance(params, dict):
+        raise ValueError("gradient compression parameters must be a dict")
+    unknown = sorted(set(params) - {"type", "threshold"})
+    if unknown:
+        raise ValueError(f"unknown gradient compression parameters {unknown}")
+    kind = params.get("type")
+    if kind is not None and not isinstance(kind, str):
+        raise ValueError(f"gradient compression type must be '2bit', 'none' or None, not {kind!r}")
+    try:
+        thr = float(torch.tensor(float(params.get("threshold", 0.5)), dtype=torch.float32))  # as the kernels see it
+    except (TypeError, ValueError):
+        raise ValueError(f"gradient compression threshold {params.get('threshold')!r} is not a number") from None
+    if not 0.0 < thr < float("inf"):
+        raise ValueError(f"gradient compression threshold must be a positive fp32 number, not {params['threshold']!r}")
+    if kind in (None, "none"):
+        return None
+    if kind != "2bit":
+        raise NotImplementedError(f"gradient compression type {kind!r} is not supported by this kvstore")
+    return thr
+
+
+def _gc_words(n: int) -> int:
+    return (n + 15) // 16
+
+
+def _quant2_torch(g: torch.Tensor, r: torch.Tensor, thr: float) -> torch.Tensor:
+    """The 2-bit push of flat fp32 ``g`` on the CPU: ``r`` updated in place, the packed int32 words returned."""
+    th = torch.tensor(thr, dtype=torch.float32)
+    t = r + g
+    pos, neg = t >= th, t <= -th
+    r.copy_(torch.where(pos, t - th, torch.where(neg, t + th, t)))
+    code = pos.to(torch.int64) + 2 * neg.to(torch.int64)
+    code = torch.nn.functional.pad(code, (0, -code.numel() % 16)).view(-1, 16)
+    w = (code << (2 * torch.arange(16))).sum(1)
+    return torch.where(w >= 1 << 31, w - (1 << 32), w).to(torch.int32)
+
+
+def _dequant2_torch(words: torch.Tensor, n: int, thr: float) -> torch.Tensor:
+    """The fp32 values of ``n`` elements packed in int32 ``words`` (CPU)."""
+    lut = torch.tensor([0.0, thr, -thr, 0.0], dtype=torch.float32)
+    codes = (words.to(torch.int64).view(-1, 1) >> (2 * torch.arange(16))) & 3
+    return lut[codes.reshape(-1)[:n]]
+
+
+def _quant2_gpu(g: torch.Tensor, r: torch.Tensor, thr: float, dst: Optional[int] = None,
+                flag: Optional[int] = None) -> Optional[torch.Tensor]:
+    """``tony_kv_quant2`` of flat fp32 ``g`` (16-B aligned) on its device's stream: the words to the device
+    address ``dst`` (counted on ``flag``), or into a new int32 tensor, which is returned."""
+    from ..ops import _lib
+
+    words = None
+    if dst is None:
+        words = torch.empty(_gc_words(g.numel()), dtype=torch.int32, device=g.device)
+        dst = words.data_ptr()
+    with torch.cuda.device(g.device):
+        _lib.check(_lib.lib().tony_kv_quant2(dst, g.data_ptr(), r.data_ptr(), g.numel(), thr, flag,
+                                             _lib.stream_ptr(g.device)), "tony_kv_quant2")
+    return words
+
+
+def _dequant2_gpu(words: torch.Tensor, n: int, thr: float, nsrc: int = 1) -> torch.Tensor:
+    """``tony_kv_dequant2``: the ordered fp32 sum of ``nsrc`` packed pushes, back to back in int32 ``words``."""
+    from ..ops import _lib
+
+    out = torch.empty(n, dtype=torch.float32, device=words.device)
+    with torch.cuda.device(words.device):
+        _lib.check(_lib.lib().tony_kv_dequant2(out.data_ptr(), words.data_ptr(), n, thr, nsrc, _gc_words(n), None,
+                                               _lib.stream_ptr(words.device)), "tony_kv_dequant2")
+    return out
+
+
+def _aligned16(g: torch.Tensor) -> torch.Tensor:
+    g = g.contiguous()
+    return g.clone() if g.data_ptr() % 16 else g  # the kernels move 16-B aligned addresses: a view at an odd offset
+
+
+class _Residuals:
+    """A worker's quantisation residual per key: fp32, on the gradient's device, zero before the first push."""
+
+    def __init__(self):
+        self.r: Dict[int, torch.Tensor] = {}
+
+    def of(self, kid: int, g: torch.Tensor) -> torch.Tensor:
+        r = self.r.get(kid)
+        if r is None:
+            r = self.r[kid] = torch.zeros_like(g)
+        elif r.device != g.device:  # (the kernel must never see a residual of another device)
+            r = self.r[kid] = r.to(g.device)
+        return r
+
+    def quantise(self, kid: int, g: torch.Tensor, thr: float) -> torch.Tensor:
+        """The int32 words of pushing flat fp32 ``g`` (on its device), by the kernel on a GPU."""
+        if g.is_cuda:
+            g = _aligned16(g)
+            return _quant2_gpu(g, self.of(kid, g), thr)
+        return _quant2_torch(g, self.of(kid, g), thr)
+
+
 class _KeyIds:
     def __init__(self):
         self.ids: Dict[object, int] = {}
@@ -199,8 +319,8 @@ class KVStore:
         self._opt = optimizer
 
     def set_gradient_compression(self, params: dict) -> None:
-        if params.get("type") not in (None, "none"):
-            raise NotImplementedError("gradient compression is not supported by this kvstore")
+        if _gc_threshold(params) is not None:  # a one-process store has no wire to compress
+            raise NotImplementedError(f"gradient compression is not supported by a {self.type!r} kvstore")
 
     def barrier(self) -> None:
         pass
@@ -403,9 +523,11 @@ class _KvPlane:
                        "tony_kv_copy_flag")
         return self.L.tony_kv_copy_blocks(nbytes)
 
-    def take(self, kid: int, w: int, numel: int, dtype: torch.dtype):
+    def take(self, kid: int, w: int, numel: int, dtype: torch.dtype, thr: Optional[float] = None):
         """Server: worker w's pushed row of kid as a new tensor, and the event after its read.  The row has
-        landed once the worker's copy counted all its workgroups on the key's push flag.  The wait and
+        landed once the worker's copy counted all its workgroups on the key's push flag (``thr``: a 2-bit
+        push -- the row holds ceil(numel / 16) words, counted by the workgroups of the worker's quantise
+        kernel, and the read decodes them).  The wait and
         the read run on the worker's own stream: the bytes may depend on a reply this server has yet to
         store (the worker pushes behind its wait for its last pull), so nothing else may queue behind
         the wait.  The worker rewrites the row only behind its wait for a later reply, which the server
@@ -417,13 +539,29 @@ class _KvPlane:
         main = torch.cuda.current_stream(self.device)
         with torch.cuda.stream(side):
             buf = torch.empty(numel, dtype=dtype, device=self.device)
-            n = self._arrived[(kid, w)] = self._arrived.get((kid, w), 0) + self.L.tony_kv_copy_blocks(nbytes)
+            blocks = self.L.tony_kv_copy_blocks(nbytes) if thr is None else self.L.tony_kv_quant_blocks(numel)
+            n = self._arrived[(kid, w)] = self._arrived.get((kid, w), 0) + blocks
             self.wait(_push_flag(slot, w), n)
-            self.copy(buf.data_ptr(), self.base + row_off + w * _pad16(nbytes), nbytes)
+            if thr is None:
+                self.copy(buf.data_ptr(), self.base + row_off + w * _pad16(nbytes), nbytes)
+            else:
+                self.decode(buf.data_ptr(), self.base + row_off + w * _pad16(nbytes), numel, thr)
             ev = torch.cuda.Event()
             ev.record(side)
         buf.record_stream(main)
         return buf, ev
+
+    def decode(self, dst: int, src: int, numel: int, thr: float) -> None:
+        """``copy`` for a row of 2-bit words: ``numel`` fp32 values decoded out of this rank's window, skipped on
+        the device like the copy when a wait of this window timed out."""
+        from ..ops import _lib
+
+        with torch.cuda.device(self.device):
+            _lib.check(self.L.tony_kv_dequant2(dst, src, numel, thr, 1, _gc_words(numel), self.window,
+                                               _lib.stream_ptr(self.device)), "tony_kv_dequant2")
+            self._polls += 1
+            if self._polls % self.POLL_EVERY == 0:
+                self.poll()
 
     def wait(self, flag_off: int, target: int) -> None:
         """Hold this rank's stream until the counter at ``flag_off`` of its window reaches ``target``."""
@@ -512,6 +650,8 @@ class _Server:
         self.deferred: Dict[int, List[int]] = {}
         self.opt: Optional[Optimizer] = None
         self.early: Dict[int, list] = {}
+        self.gc: Optional[float] = None  # 2-bit gradient compression threshold (OP_GC)
+        self.early_gc: list = []  # compressed pushes that arrived before the setting
         self.sends = []
         self.applied = 0
         self.round: Dict[int, list] = {}  # kid -> [(worker, arrival, payload, event)] of the open round
@@ -550,11 +690,24 @@ class _Server:
 
     def handle(self, worker: int, hdr: List[int], buf: Optional[torch.Tensor] = None) -> bool:
         op, kid, numel, dcode = hdr
-        if op in (OP_INIT, OP_PUSH, OP_OPT) and buf is None:
+        if op in (OP_INIT, OP_PUSH, OP_OPT, OP_GC) and buf is None:
             buf = torch.empty(numel, dtype=_DTYPES[dcode])
             dist.recv(buf, worker, tag=TAG_DATA)
+        if op == OP_GC:  # the workers' set_gradient_compression, shipped by rank 0 (kid: this server)
+            self.gc = _gc_threshold(json.loads(bytes(buf.tolist()).decode()))
+            parked, self.early_gc = self.early_gc, []
+            for w, h, b in parked:
+                self.handle(w, h, b)
+            return True
+        if op == OP_PUSH_C and buf is None:
+            buf = torch.empty(_gc_words(numel), dtype=torch.int32)
+            dist.recv(buf, worker, tag=TAG_DATA)
+        if op in (OP_PUSH_C, OP_PUSH_CX) and self.gc is None:
+            # raced ahead of rank 0's setting (sent before the workers' barrier, like an INIT): replay once it is here
+            self.early_gc.append((worker, hdr, buf))
+            return True
         via = op == OP_PULL_X
-        if op in (OP_PUSH, OP_PULL, OP_PUSH_X, OP_PULL_X) and kid not in self.values:
+        if op in (OP_PUSH, OP_PULL, OP_PUSH_X, OP_PULL_X, OP_PUSH_C, OP_PUSH_CX) and kid not in self.values:
             # raced ahead of worker 0's INIT (it is sent before the workers' barrier, but the server
             # may poll this worker first): replay once the key exists.  A plane push is parked with its
             # raw header: the key has no window row in this server's layout until the INIT adds it, and
@@ -564,6 +717,16 @@ class _Server:
         ev = None
         if op == OP_PUSH_X:  # the payload is in this worker's receive row of the window: take it now
             buf, ev = self.plane.take(kid, worker - self.topo.num_servers, numel, _DTYPES[dcode])
+            op = OP_PUSH
+        elif op == OP_PUSH_CX:  # 2-bit words in the row: the read decodes them
+            buf, ev = self.plane.take(kid, worker - self.topo.num_servers, numel, torch.float32, self.gc)
+            op = OP_PUSH
+        elif op == OP_PUSH_C:  # 2-bit words over gloo: decoded on the value's device
+            v = self.values[kid]
+            if v.is_cuda:
+                buf = _dequant2_gpu(buf.to(v.device), numel, self.gc)
+            else:
+                buf = _dequant2_torch(buf, numel, self.gc)
             op = OP_PUSH
         elif op == OP_PULL_X:
             op = OP_PULL
@@ -650,6 +813,10 @@ class DistKVStore(KVStore):
         # in between must not let the server overwrite that area before the copy read it
         self._landed: Dict[int, "torch.cuda.Event"] = {}
         self.plane_ops = [0, 0]  # pushes / pulls whose payload went over the GPU plane (tests)
+        self._gc: Optional[float] = None  # 2-bit gradient compression threshold (set_gradient_compression)
+        self._res = _Residuals()
+        self._pushed = False
+        self.compressed_ops = [0, 0]  # 2-bit pushes whose words went over the GPU plane / over gloo (tests)
         self._closed = False
 
     @property
@@ -686,6 +853,10 @@ class DistKVStore(KVStore):
         for k, v in zip(*self._keys_vals(key, value)):
             kid = self._key(k)
             g = _merge(_as_list(v)).reshape(-1)
+            self._pushed = True
+            if self._gc is not None and g.dtype == torch.float32:
+                self._push_2bit(kid, g)
+                continue
             if self._on_plane(kid, g) and kid not in self._unread:
                 srv, nbytes, row_off, _, slot = self.plane.keys[kid]
                 g = g.to(self.plane.device).contiguous()
@@ -701,6 +872,42 @@ class DistKVStore(KVStore):
                 self.plane_ops[0] += 1
                 continue
             self._send(OP_PUSH, kid, g.cpu().contiguous())
+
+    def _push_2bit(self, kid: int, g: torch.Tensor) -> None:
+        """A push of the merged flat fp32 gradient with 2-bit compression on (module docstring)."""
+        srv = self.topo.server_of(kid)
+        hdr = [kid, g.numel(), _dcode(g.dtype)]
+        if self._on_plane(kid, g) and kid not in self._unread:
+            _, nbytes, row_off, _, slot = self.plane.keys[kid]
+            g = _aligned16(g.to(self.plane.device))
+            # one kernel: the residual updated in place, the words straight into this worker's row of the
+            # server's window (they fit it: 4 B per 16 elements), counted on the key's push flag there
+            _quant2_gpu(g, self._res.of(kid, g), self._gc, self.plane.peer[srv] + row_off + self.rank * _pad16(nbytes),
+                        self.plane.peer_win[srv] + _push_flag(slot, self.rank))
+            dist.send(torch.tensor([OP_PUSH_CX] + hdr, dtype=torch.int64), srv, tag=TAG_HDR)
+            self._unread.add(kid)
+            self.plane_ops[0] += 1
+            self.compressed_ops[0] += 1
+            return
+        # off the plane, a re-push before a pull (the row may be unread) or a CPU tensor: the words over gloo
+        words = self._res.quantise(kid, g, self._gc).cpu()
+        dist.send(torch.tensor([OP_PUSH_C] + hdr, dtype=torch.int64), srv, tag=TAG_HDR)
+        dist.send(words, srv, tag=TAG_DATA)
+        self.compressed_ops[1] += 1
+
+    def set_gradient_compression(self, params: dict) -> None:
+        """Collective over the workers, like ``set_optimizer``: rank 0 ships the setting to every server.  Allowed
+        until the first push (a residual and the servers' decoding must cover every push of a key alike)."""
+        thr = _gc_threshold(params)
+        if self._pushed:
+            raise RuntimeError("set_gradient_compression must be called before the first push")
+        if self.rank == 0:
+            cfg = json.dumps({"type": "none" if thr is None else "2bit", "threshold": thr if thr else 0.5})
+            payload = torch.tensor(list(cfg.encode()), dtype=torch.uint8)
+            for s in range(self.topo.num_servers):
+                self._send_to(s, OP_GC, payload)
+        self._gc = thr
+        self.barrier()
 
     def pull(self, key, out=None, priority: int = 0, ignore_sparse: bool = True):  # noqa: ARG002
         keys, outs = self._keys_vals(key, out)
@@ -780,6 +987,9 @@ class DeviceSyncKVStore(KVStore):
 
             init_from_env()
         self.group = group
+        self._gc: Optional[float] = None  # 2-bit gradient compression threshold (set_gradient_compression)
+        self._res = _Residuals()
+        self._pushed = False
 
     @property
     def rank(self) -> int:
@@ -798,8 +1008,34 @@ class DeviceSyncKVStore(KVStore):
     def push(self, key, value, priority: int = 0) -> None:  # noqa: ARG002
         for k, v in zip(*self._keys_vals(key, value)):
             g = _merge(_as_list(v))
+            self._pushed = True
+            if self._gc is not None and g.dtype == torch.float32:
+                self._apply(self._key(k), self._allgather_2bit(self._key(k), g.reshape(-1)).view(g.shape))
+                continue
             dist.all_reduce(g, group=self.group)
             self._apply(self._key(k), g)
+
+    def _allgather_2bit(self, kid: int, g: torch.Tensor) -> torch.Tensor:
+        """The workers' 2-bit pushes of flat fp32 ``g``: the words all-gathered, the decoded values summed in
+        rank order (``acc = v_0; acc += v_1; ...``), identically on every worker."""
+        n, nw = g.numel(), self.num_workers
+        words = self._res.quantise(kid, g, self._gc)
+        gathered = torch.empty(nw, _gc_words(n), dtype=torch.int32, device=words.device)
+        dist.all_gather(list(gathered.unbind(0)), words, group=self.group)
+        if gathered.is_cuda:
+            return _dequant2_gpu(gathered, n, self._gc, nsrc=nw)
+        acc = _dequant2_torch(gathered[0], n, self._gc)
+        for r in range(1, nw):
+            acc += _dequant2_torch(gathered[r], n, self._gc)
+        return acc
+
+    def set_gradient_compression(self, params: dict) -> None:
+        """Collective over the workers; allowed until the first push."""
+        thr = _gc_threshold(params)
+        if self._pushed:
+            raise RuntimeError("set_gradient_compression must be called before the first push")
+        self._gc = thr
+        self.barrier()
 
     def barrier(self) -> None:
         dist.barrier(group=self.group)
