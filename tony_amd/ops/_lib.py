@@ -226,6 +226,15 @@ _SIGNATURES = {
     "tony_kv_quant_blocks": [c_int64],
     "tony_kv_quant2": [c_void_p, c_void_p, c_void_p, c_int64, c_float, c_void_p, c_void_p],
     "tony_kv_dequant2": [c_void_p, c_void_p, c_int64, c_float, c_int, c_int64, c_void_p, c_void_p],
+    # row-sparse keys of the kvstore (dst_rows, table, ids, nnz, row_bytes, R, flag, window | dst_rows, union_ids,
+    # nu, host arrays of the sources' id / row addresses and row counts, nsrc, row_elems | weight, mom, ids, rows,
+    # nnz, row_elems, R, lr, momentum, wd, rescale, has_clip, clip)
+    "tony_kv_rsp_gather_blocks": [c_int64, c_int64],
+    "tony_kv_rsp_gather": [c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_int64, c_void_p, c_void_p, c_void_p],
+    "tony_kv_rsp_merge": [c_void_p, c_void_p, c_int64, ctypes.POINTER(c_int64), ctypes.POINTER(c_int64),
+                          ctypes.POINTER(c_int64), c_int, c_int64, c_void_p],
+    "tony_kv_rsp_sgd": [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_int64, c_float, c_float, c_float,
+                        c_float, c_int, c_float, c_void_p],
     "tony_ps_max_buckets": [],
     "tony_ps_max_blocks": [],
     "tony_ps_land_entry_bytes": [],

@@ -712,3 +712,268 @@ TONY_API int tony_kv_dequant2(float* dst, const uint32_t* words, int64_t n, floa
   TONY_LAUNCH_CHECK();
   return 0;
 }
+
+// ------------------------------------------------------------------------ kvstore row-sparse keys --
+// kv.RowSparse of parallel/kvstore.py: nnz rows of a dense [R, row] fp32 table named by sorted int64 ids.  Rows
+// are moved as 16-B chunks (row bytes a multiple of 16).  One work item is (row i, pass p): a wave takes the
+// consecutive chunks [64 p, 64 p + 64) of ONE row -- the row id is wave-uniform (read through scalar loads) and
+// every access of the wave is one contiguous run.  Items are dealt to the waves of a bounded grid.  An id
+// outside [0, R) is skipped (the host rejected it already: no upstream bug may turn into a wild address).
+namespace {
+
+constexpr int kRspMaxSrc = 64;  // parallel/kvstore.py _MAX_KV_WORKERS
+
+struct RspSources {
+  const int64_t* ids[kRspMaxSrc];  // sorted, strictly increasing
+  const float* rows[kRspMaxSrc];
+  int64_t nnz[kRspMaxSrc];
+};
+
+struct RspSgd {
+  float lr, momentum, wd, rescale, clip;
+  int has_clip;
+};
+
+// One separately rounded fp32 operation each.  (hip's __fmul_rn / __fadd_rn are the plain operators compiled under the
+// default contraction mode: a product and a sum made of them may still meet in one fma.  These carry no such leave.)
+__device__ __forceinline__ float rn_mul(float a, float b) {
+#pragma clang fp contract(off)
+  return a * b;
+}
+__device__ __forceinline__ float rn_add(float a, float b) {
+#pragma clang fp contract(off)
+  return a + b;
+}
+__device__ __forceinline__ float rn_sub(float a, float b) {
+#pragma clang fp contract(off)
+  return a - b;
+}
+
+__device__ __forceinline__ int64_t rsp_first_item() {
+  return static_cast<int64_t>(blockIdx.x) * 4 + __builtin_amdgcn_readfirstlane(static_cast<int>(threadIdx.x >> 6));
+}
+
+int kv_rsp_blocks(int64_t nnz, int64_t rc) {
+  const int64_t items = nnz * ((rc + 63) >> 6);
+  return static_cast<int>(std::min<int64_t>(1024, (items + 3) / 4));
+}
+
+// item `it` of a gather: this lane's chunk of its row into v and the chunk's place in dst_rows, or -1 for no chunk
+// (past the items, past the row's end, an id outside the table)
+__device__ __forceinline__ int64_t rsp_gather_load(const uint4* __restrict__ table, const int64_t* __restrict__ ids,
+                                                   int64_t it, int64_t items, int64_t passes, int64_t rc, int64_t R,
+                                                   int lane, uint4& v) {
+  v = make_uint4(0u, 0u, 0u, 0u);
+  if (it >= items) return -1;
+  const int64_t i = passes == 1 ? it : it / passes;
+  const int64_t c = (it - i * passes) * 64 + lane;
+  const int64_t id = ids[i];
+  if (static_cast<uint64_t>(id) >= static_cast<uint64_t>(R) || c >= rc) return -1;
+  v = table[id * rc + c];
+  return i * rc + c;
+}
+
+// dst_rows[i] = table[ids[i]].  err (nullable): see kv_copy_kernel; flag (nullable): the hand-off of
+// kv_copy_flag_kernel, one add per workgroup after its bytes.
+__global__ __launch_bounds__(256) void kv_rsp_gather_kernel(const uint4* __restrict__ table, uint4* __restrict__ dst,
+                                                            const int64_t* __restrict__ ids, int64_t nnz, int64_t rc,
+                                                            int64_t R, uint32_t* flag, const int* err) {
+  if (err != nullptr && __hip_atomic_load(err, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM) != 0) return;
+  const int lane = threadIdx.x & 63;
+  const int64_t passes = (rc + 63) >> 6, items = nnz * passes, waves = static_cast<int64_t>(gridDim.x) * 4;
+  // four items a turn, each with a wave-uniform row: their id loads, then their row loads, are in flight together
+  // (a short row leaves most of a wave's lanes idle, so one item at a time waits out two latencies per 256 B)
+  for (int64_t it0 = rsp_first_item(); it0 < items; it0 += 4 * waves) {
+    uint4 v0, v1, v2, v3;
+    const int64_t a0 = rsp_gather_load(table, ids, it0, items, passes, rc, R, lane, v0);
+    const int64_t a1 = rsp_gather_load(table, ids, it0 + waves, items, passes, rc, R, lane, v1);
+    const int64_t a2 = rsp_gather_load(table, ids, it0 + 2 * waves, items, passes, rc, R, lane, v2);
+    const int64_t a3 = rsp_gather_load(table, ids, it0 + 3 * waves, items, passes, rc, R, lane, v3);
+    if (a0 >= 0) dst[a0] = v0;
+    if (a1 >= 0) dst[a1] = v1;
+    if (a2 >= 0) dst[a2] = v2;
+    if (a3 >= 0) dst[a3] = v3;
+  }
+  if (flag != nullptr) {
+    __threadfence_system();  // this workgroup's rows are visible to the consumer before its add
+    __syncthreads();
+    if (threadIdx.x == 0) __hip_atomic_fetch_add(flag, 1u, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
+  }
+}
+
+// dst_rows[u] = the ordered sum over the sources that hold union id u: acc = first; acc = acc + next; ... one
+// fp32 add each, in source order (the order a server merges a round in).  A union id no source holds gives a
+// zero row.  A workgroup takes tiles of 64 union rows in two steps.  Search: wave w looks the tile's ids up in
+// sources w, w + 4, ... -- the source is wave-uniform, lane l searches the id of row l in that source's sorted ids
+// (a binary search per lane: 64 of them in flight per wave in place of one) and leaves the row's position, or -1,
+// in LDS.  Move: wave w takes rows w, w + 4, ... of the tile, the row wave-uniform again, reads the positions back
+// (a broadcast) and adds the sources' chunks in order.
+constexpr int kMergeTile = 64;
+
+__global__ __launch_bounds__(256) void kv_rsp_merge_kernel(RspSources S, int nsrc, const int64_t* __restrict__ uids,
+                                                           int64_t nu, int64_t rc, float4* __restrict__ dst) {
+  extern __shared__ int32_t merge_pos[];  // [nsrc][kMergeTile]
+  const int lane = threadIdx.x & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(static_cast<int>(threadIdx.x >> 6));
+  const int64_t tiles = (nu + kMergeTile - 1) / kMergeTile;
+  for (int64_t t = blockIdx.x; t < tiles; t += gridDim.x) {
+    const int64_t u0 = t * kMergeTile;
+    const int rows = static_cast<int>(min(static_cast<int64_t>(kMergeTile), nu - u0));
+    for (int s = wave; s < nsrc; s += 4) {
+      const int64_t* sid = S.ids[s];
+      const int64_t n = S.nnz[s];
+      int32_t found = -1;
+      if (lane < rows) {
+        const int64_t id = uids[u0 + lane];
+        int64_t lo = 0, hi = n;
+        while (lo < hi) {
+          const int64_t mid = (lo + hi) >> 1;
+          if (sid[mid] < id) lo = mid + 1; else hi = mid;
+        }
+        if (lo < n && sid[lo] == id) found = static_cast<int32_t>(lo);
+      }
+      merge_pos[s * kMergeTile + lane] = found;
+    }
+    __syncthreads();
+    for (int r = wave; r < rows; r += 4) {
+      for (int64_t c = lane; c < rc; c += 64) {
+        float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
+        bool have = false;
+        for (int s = 0; s < nsrc; ++s) {
+          const int p = __builtin_amdgcn_readfirstlane(merge_pos[s * kMergeTile + r]);
+          if (p < 0) continue;
+          const float4 v = *reinterpret_cast<const float4*>(S.rows[s] + (static_cast<int64_t>(p) * rc + c) * 4);
+          if (have)
+            acc = make_float4(rn_add(acc.x, v.x), rn_add(acc.y, v.y), rn_add(acc.z, v.z), rn_add(acc.w, v.w));
+          else
+            acc = v;
+          have = true;
+        }
+        dst[(u0 + r) * rc + c] = acc;
+      }
+    }
+    __syncthreads();  // every wave has read the tile's positions before the next tile's are written
+  }
+}
+
+// one element of the lazy SGD contract (parallel/kvstore.py module docstring): every line one rounded fp32 operation
+template <bool MOM>
+__device__ __forceinline__ void rsp_sgd1(float& w, float& m, float g, const RspSgd& hp) {
+  const float g1 = rn_mul(g, hp.rescale);
+  const float g2 = hp.has_clip ? (g1 > hp.clip ? hp.clip : (g1 < -hp.clip ? -hp.clip : g1)) : g1;  // a NaN stays
+  const float p = rn_mul(hp.wd, w);
+  const float g3 = rn_add(g2, p);
+  const float s = rn_mul(hp.lr, g3);
+  if constexpr (MOM) {
+    m = rn_mul(hp.momentum, m);
+    m = rn_sub(m, s);
+    w = rn_add(w, m);
+  } else {
+    w = rn_sub(w, s);
+  }
+}
+
+// the touched rows ids[0, nnz) of weight (and momentum) updated in place from the compact gradient rows; ids
+// strictly increasing: no row is written by two waves
+template <bool MOM>
+__global__ __launch_bounds__(256) void kv_rsp_sgd_kernel(float4* __restrict__ weight, float4* __restrict__ mom,
+                                                         const int64_t* __restrict__ ids,
+                                                         const float4* __restrict__ rows, int64_t nnz, int64_t rc,
+                                                         int64_t R, RspSgd hp) {
+  const int lane = threadIdx.x & 63;
+  const int64_t passes = (rc + 63) >> 6, items = nnz * passes;
+  for (int64_t it = rsp_first_item(); it < items; it += static_cast<int64_t>(gridDim.x) * 4) {
+    const int64_t i = passes == 1 ? it : it / passes;
+    const int64_t c = (it - i * passes) * 64 + lane;
+    const int64_t id = ids[i];
+    if (static_cast<uint64_t>(id) >= static_cast<uint64_t>(R) || c >= rc) continue;
+    const float4 g = rows[i * rc + c];
+    float4 w = weight[id * rc + c];
+    float4 m = make_float4(0.f, 0.f, 0.f, 0.f);
+    if constexpr (MOM) m = mom[id * rc + c];
+    rsp_sgd1<MOM>(w.x, m.x, g.x, hp);
+    rsp_sgd1<MOM>(w.y, m.y, g.y, hp);
+    rsp_sgd1<MOM>(w.z, m.z, g.z, hp);
+    rsp_sgd1<MOM>(w.w, m.w, g.w, hp);
+    weight[id * rc + c] = w;
+    if constexpr (MOM) mom[id * rc + c] = m;
+  }
+}
+
+inline bool misaligned(const void* p, uintptr_t mask) { return (reinterpret_cast<uintptr_t>(p) & mask) != 0; }
+
+}  // namespace
+
+// workgroups of one tony_kv_rsp_gather launch (what a flagged gather adds to the consumer's counter)
+TONY_API int tony_kv_rsp_gather_blocks(int64_t nnz, int64_t row_bytes) {
+  return (nnz <= 0 || row_bytes <= 0 || (row_bytes & 15)) ? 0 : kv_rsp_blocks(nnz, row_bytes >> 4);
+}
+
+// dst_rows[i] <- table[ids[i]] for i < nnz, rows of row_bytes (a multiple of 16) of a table of R rows; dst_rows
+// may be a mapped peer window.  flag (nullable): one add per workgroup, tony_kv_rsp_gather_blocks in all;
+// window (nullable): write nothing when that window's error word is set
+TONY_API int tony_kv_rsp_gather(void* dst_rows, const void* table, const void* ids, int64_t nnz, int64_t row_bytes,
+                                int64_t R, void* flag, void* window, hipStream_t stream) {
+  if (dst_rows == nullptr || table == nullptr || ids == nullptr || nnz < 0 || row_bytes <= 0 || (row_bytes & 15) ||
+      R <= 0 || misaligned(dst_rows, 15) || misaligned(table, 15) || misaligned(ids, 7) || misaligned(flag, 3))
+    return -1;
+  if (nnz == 0) return 0;
+  const int64_t rc = row_bytes >> 4;
+  kv_rsp_gather_kernel<<<kv_rsp_blocks(nnz, rc), 256, 0, stream>>>(
+      static_cast<const uint4*>(table), static_cast<uint4*>(dst_rows), static_cast<const int64_t*>(ids), nnz, rc, R,
+      static_cast<uint32_t*>(flag),
+      window == nullptr ? nullptr : reinterpret_cast<const int*>(static_cast<const uint8_t*>(window) + kErrOff));
+  TONY_LAUNCH_CHECK();
+  return 0;
+}
+
+// dst_rows[u] (nu rows of row_elems fp32) <- the ordered sum of the rows the nsrc sources hold for union_ids[u].
+// src_ids / src_rows: host arrays of nsrc device addresses, src_nnz: host array of the sources' row counts (a
+// source of 0 rows may have null addresses)
+TONY_API int tony_kv_rsp_merge(float* dst_rows, const int64_t* union_ids, int64_t nu, const int64_t* src_ids,
+                               const int64_t* src_rows, const int64_t* src_nnz, int nsrc, int64_t row_elems,
+                               hipStream_t stream) {
+  if (dst_rows == nullptr || union_ids == nullptr || nu < 0 || src_ids == nullptr || src_rows == nullptr ||
+      src_nnz == nullptr || nsrc < 1 || nsrc > kRspMaxSrc || row_elems <= 0 || (row_elems & 3) ||
+      misaligned(dst_rows, 15) || misaligned(union_ids, 7))
+    return -1;
+  RspSources S{};
+  for (int s = 0; s < nsrc; ++s) {
+    S.ids[s] = reinterpret_cast<const int64_t*>(static_cast<uintptr_t>(src_ids[s]));
+    S.rows[s] = reinterpret_cast<const float*>(static_cast<uintptr_t>(src_rows[s]));
+    S.nnz[s] = src_nnz[s];
+    if (S.nnz[s] < 0 || S.nnz[s] > INT32_MAX || (S.nnz[s] > 0 && (S.ids[s] == nullptr || S.rows[s] == nullptr)) || misaligned(S.ids[s], 7) ||
+        misaligned(S.rows[s], 15))
+      return -1;
+  }
+  if (nu == 0) return 0;
+  const int blocks = static_cast<int>(std::min<int64_t>(1024, (nu + kMergeTile - 1) / kMergeTile));
+  kv_rsp_merge_kernel<<<blocks, 256, static_cast<size_t>(nsrc) * kMergeTile * sizeof(int32_t), stream>>>(
+      S, nsrc, union_ids, nu, row_elems >> 2, reinterpret_cast<float4*>(dst_rows));
+  TONY_LAUNCH_CHECK();
+  return 0;
+}
+
+// the lazy SGD contract on rows ids[0, nnz) of weight [R, row_elems] (and mom, null when momentum is 0) from the
+// compact gradient rows, in one launch; clip is read only when has_clip
+TONY_API int tony_kv_rsp_sgd(float* weight, float* mom, const int64_t* ids, const float* rows, int64_t nnz,
+                             int64_t row_elems, int64_t R, float lr, float momentum, float wd, float rescale,
+                             int has_clip, float clip, hipStream_t stream) {
+  if (weight == nullptr || ids == nullptr || rows == nullptr || nnz < 0 || row_elems <= 0 || (row_elems & 3) ||
+      R <= 0 || misaligned(weight, 15) || misaligned(mom, 15) || misaligned(rows, 15) || misaligned(ids, 7) ||
+      (mom == nullptr) != (momentum == 0.f))
+    return -1;
+  if (nnz == 0) return 0;
+  const int64_t rc = row_elems >> 2;
+  const RspSgd hp{lr, momentum, wd, rescale, clip, has_clip};
+  const int blocks = kv_rsp_blocks(nnz, rc);
+  if (mom != nullptr)
+    kv_rsp_sgd_kernel<true><<<blocks, 256, 0, stream>>>(reinterpret_cast<float4*>(weight),
+                                                        reinterpret_cast<float4*>(mom), ids,
+                                                        reinterpret_cast<const float4*>(rows), nnz, rc, R, hp);
+  else
+    kv_rsp_sgd_kernel<false><<<blocks, 256, 0, stream>>>(reinterpret_cast<float4*>(weight), nullptr, ids,
+                                                         reinterpret_cast<const float4*>(rows), nnz, rc, R, hp);
+  TONY_LAUNCH_CHECK();
+  return 0;
+}

@@ -58,6 +58,40 @@ on the key's push flag by ``tony_kv_quant_blocks(n)`` workgroups: 0.25 B per ele
 the words.  ``dist_device_sync`` all-gathers the words and every worker sums the decoded pushes in rank order.
 The call is collective over the workers like ``set_optimizer`` (rank 0 ships the setting to the servers) and is
 allowed until the first push; a store that never gets it takes none of this code.
+
+Row-sparse keys (``RowSparse``, ``row_sparse_pull``): a key whose ``init`` value is a ``RowSparse`` is a sparse key;
+its stored value is the dense ``[R, ...]`` tensor.  ``RowSparse(indices, data, shape)`` names ``nnz`` rows by int64
+``indices``, strictly increasing and in ``[0, R)`` (checked at construction: one host synchronisation for GPU
+tensors, before any kernel); ``RowSparse.from_rows`` builds one from unsorted ids with duplicates (stable sort, the
+duplicates of a row summed in order of occurrence, one fp32 add each).  A sparse key is pushed ``RowSparse`` values
+only, a dense key tensors only (``TypeError`` otherwise); ``pull(ignore_sparse=True)`` skips sparse keys,
+``ignore_sparse=False`` pulls them dense; ``row_sparse_pull(key, out, row_ids)`` leaves the sorted unique
+``row_ids`` in ``out.indices`` and those rows of the stored value in ``out.data`` (out-of-range ids: ``ValueError``
+on the caller, nothing sent), and in ``dist_sync`` waits for the worker's own pushed round as ``pull`` does.
+Merging is fully ordered: a pushed list in list order, a ``dist_sync`` round in worker order, ``dist_device_sync``
+in rank order; the merged index set is the sorted union and a merged row is ``acc = first source having it; acc =
+acc + next source having it; ...``, one fp32 add each.  With no optimizer the store takes the merged push as its
+value (rows not pushed become zero); with one, only the merged rows of the weight and of the optimizer's state
+(dense ``[R, ...]``, zero at first use) change -- every other row keeps its bits.  Lazy SGD, per element of a
+touched row, every line one separately rounded fp32 operation (no contraction)::
+
+    g1 = g * rescale_grad
+    g2 = clip_gradient is None ? g1 : (g1 > c ? c : (g1 < -c ? -c : g1))   # a NaN stays NaN
+    p  = wd * w ;  g3 = g2 + p
+    momentum == 0:  s = lr * g3 ; w = w - s
+    momentum != 0:  m = momentum * m ; s = lr * g3 ; m = m - s ; w = w + m
+
+fp32 GPU keys whose rows are a multiple of 16 B run this in one kernel (``tony_kv_rsp_sgd``), their merges in
+``tony_kv_rsp_merge`` and their row reads in ``tony_kv_rsp_gather``; lazy Adam, CPU keys and other dtypes or row
+lengths gather the touched rows of weight and state, run ``Optimizer.update`` on them and scatter them back (Adam's
+``t`` counts updates of the key).  On the wire a sparse push is the header (``numel`` = ``nnz``), the ids, the rows;
+on the plane the worker stores rows, then ids, into its row of the server's window (two flagged copies) when
+``nnz * row_bytes + pad16(8 * nnz) <= pad16(key bytes)`` and the key's row is known to be read, else over gloo;
+``nnz == 0`` sends the header only.  A ``row_sparse_pull`` sends its unique ids over gloo (8 B per row against
+``row_bytes``; the host needs ``nnz`` anyway: one synchronisation per call) and the server gathers the rows straight
+into the worker's landing area, counted on the worker's reply flag; the ordering rules of the dense pull apply
+unchanged.  ``dist_device_sync`` all-gathers ``nnz``, then ids and rows padded to the largest.  A ``RowSparse`` push
+ignores the gradient-compression setting, as MXNet's does.  A store that never sees a ``RowSparse`` runs none of this.
 """
 from __future__ import annotations
 
@@ -74,6 +108,10 @@ OP_INIT, OP_PUSH, OP_PULL, OP_OPT, OP_STOP, OP_PUSH_X, OP_PULL_X = range(7)  # _
 # gradient compression: the setting (JSON, like OP_OPT), a 2-bit push with its words over gloo (the header keeps
 # the gradient's numel; the payload is ceil(numel / 16) int32 words) and one with its words on the GPU plane
 OP_GC, OP_PUSH_C, OP_PUSH_CX = 7, 8, 9
+# row-sparse keys (numel carries nnz): init of a sparse key (the dense payload, then int64 [R]); a push over gloo
+# (int64 [ids..., row elements], then the rows) and on the GPU plane; a row_sparse_pull answered over gloo and on
+# the plane (both: the ids follow the header over gloo)
+OP_INIT_RSP, OP_PUSH_RSP, OP_PUSH_RSPX, OP_PULL_RSP, OP_PULL_RSPX = 10, 11, 12, 13, 14
 TAG_HDR, TAG_DATA, TAG_REPLY = 1, 2, 3
 _DTYPES = [torch.float32, torch.float16, torch.bfloat16, torch.float64, torch.int64, torch.int32, torch.uint8]
 _EXIT_KEY = "tony/kv/exited"
@@ -132,6 +170,53 @@ class Optimizer:
             w.addcdiv_(m, v.sqrt().add_(c["epsilon"]), value=-lr_t)
         if w is not weight:
             weight.copy_(w)
+
+    _ROW_STATE = {"sgd": ("mom",), "adam": ("m", "v")}
+
+    def _row_state(self, key: int, weight: torch.Tensor):
+        """A sparse key's state and the names of its tensors: dense fp32 ``[R, ...]``, zero at first use."""
+        st = self.state.setdefault(key, {"t": 0})
+        names = [n for n in self._ROW_STATE[self.name] if self.name == "adam" or self.cfg["momentum"]]
+        for n in names:
+            if n not in st:
+                st[n] = torch.zeros(weight.shape, dtype=torch.float32, device=weight.device)
+        return st, names
+
+    def update_rows(self, key: int, weight: torch.Tensor, ids: torch.Tensor, grad_rows: torch.Tensor) -> None:
+        """The lazy update of a row-sparse key (module docstring): rows ``ids`` (sorted, unique, in range) of the
+        dense ``weight`` [R, ...] and of its state from the compact ``grad_rows``; every other row keeps its bits."""
+        c = self.cfg
+        st, names = self._row_state(key, weight)
+        re = _row_elems(weight.shape)
+        if (self.name == "sgd" and _rsp_kernel_rows(weight, re) and weight.is_contiguous()
+                and weight.data_ptr() % 16 == 0 and grad_rows.dtype == torch.float32):
+            from ..ops import _lib
+
+            if not ids.numel():  # no row to touch (and no address of an empty tensor to hand to a launcher)
+                return
+            ids, g = _aligned16(ids), _aligned16(grad_rows)
+            mom = st["mom"].data_ptr() if names else None
+            clip = c["clip_gradient"]
+            with torch.cuda.device(weight.device):
+                _lib.check(_lib.lib().tony_kv_rsp_sgd(
+                    weight.data_ptr(), mom, ids.data_ptr(), g.data_ptr(), ids.numel(), re, weight.shape[0],
+                    c["learning_rate"], c["momentum"], c["wd"], c["rescale_grad"], int(clip is not None),
+                    0.0 if clip is None else clip, _lib.stream_ptr(weight.device)), "tony_kv_rsp_sgd")
+            return
+        self.update_rows_generic(key, weight, ids, grad_rows)
+
+    def update_rows_generic(self, key: int, weight: torch.Tensor, ids: torch.Tensor, grad_rows: torch.Tensor) -> None:
+        """``update_rows`` for any optimizer, device and dtype: the touched rows of weight and state gathered,
+        the dense update's math on them, scattered back."""
+        st, names = self._row_state(key, weight)
+        rows = Optimizer(**self.cfg)
+        rows.state[key] = {"t": st["t"], **{n: st[n].index_select(0, ids) for n in names}}
+        w = weight.index_select(0, ids)
+        rows.update(key, w, grad_rows)
+        weight.index_copy_(0, ids, w)
+        for n in names:
+            st[n].index_copy_(0, ids, rows.state[key][n])
+        st["t"] = rows.state[key]["t"]
 
     def state_dict(self):
         return {"cfg": self.cfg, "state": self.state}
@@ -253,6 +338,147 @@ class _Residuals:
         return _quant2_torch(g, self.of(kid, g), thr)
 
 
+# -- row-sparse values (module docstring) -------------------------------------------------------
+class RowSparse:
+    """``nnz`` rows of a dense ``shape`` tensor: int64 ``indices`` [nnz], strictly increasing and in
+    ``[0, shape[0])``, and ``data`` [nnz, *shape[1:]] on the same device."""
+
+    def __init__(self, indices: torch.Tensor, data: torch.Tensor, shape, _checked: bool = False):
+        self.shape = tuple(int(d) for d in shape)
+        if not self.shape or self.shape[0] < 0:
+            raise ValueError(f"a RowSparse needs a shape of at least one dimension, not {shape!r}")
+        if indices.dtype != torch.int64 or indices.dim() != 1:
+            raise ValueError("RowSparse indices must be an int64 vector")
+        if tuple(data.shape) != (indices.numel(),) + self.shape[1:]:
+            raise ValueError(f"RowSparse data of shape {tuple(data.shape)} does not hold {indices.numel()} rows of "
+                             f"shape {self.shape[1:]}")
+        if indices.device != data.device:
+            raise ValueError("RowSparse indices and data must be on the same device")
+        if not _checked and indices.numel():
+            bad = (indices[0] < 0) | (indices[-1] >= self.shape[0]) | (indices[1:] <= indices[:-1]).any()
+            if bool(bad):  # (the one host synchronisation of a GPU value)
+                raise ValueError(f"RowSparse indices must be strictly increasing and in [0, {self.shape[0]})")
+        self.indices, self.data = indices, data
+
+    @property
+    def nnz(self) -> int:
+        return self.indices.numel()
+
+    def to_dense(self) -> torch.Tensor:
+        out = torch.zeros(self.shape, dtype=self.data.dtype, device=self.data.device)
+        if self.nnz:
+            out.index_copy_(0, self.indices, self.data)
+        return out
+
+    @classmethod
+    def from_rows(cls, ids: torch.Tensor, rows: torch.Tensor, shape) -> "RowSparse":
+        """From unsorted ``ids`` with duplicates (an embedding's backward): stable sort, the rows of one id summed
+        in order of occurrence as fp32 adds, left to right."""
+        ids = ids.reshape(-1).to(torch.int64)
+        shape = tuple(int(d) for d in shape)
+        rows = rows.reshape((ids.numel(),) + shape[1:])
+        if ids.numel() and (int(ids.min()) < 0 or int(ids.max()) >= shape[0]):
+            raise ValueError(f"row ids must be in [0, {shape[0]})")
+        sid, order = torch.sort(ids, stable=True)
+        uniq, counts = torch.unique_consecutive(sid, return_counts=True)
+        starts = torch.cumsum(counts, 0) - counts
+        acc = rows.index_select(0, order.index_select(0, starts)).float()
+        for k in range(1, int(counts.max()) if ids.numel() else 0):
+            sel = (counts > k).nonzero().reshape(-1)
+            nxt = rows.index_select(0, order.index_select(0, starts.index_select(0, sel) + k)).float()
+            acc.index_copy_(0, sel, acc.index_select(0, sel) + nxt)
+        return cls(uniq, acc.to(rows.dtype), shape, _checked=True)
+
+
+def _rsp_kernel_rows(t: torch.Tensor, row_elems: int) -> bool:
+    """Whether the row-sparse kernels take rows of ``t``: fp32 on a GPU, the row a multiple of 16 B."""
+    return t.is_cuda and t.dtype == torch.float32 and row_elems > 0 and row_elems % 4 == 0
+
+
+def _row_elems(shape) -> int:
+    n = 1
+    for d in shape[1:]:
+        n *= int(d)
+    return n
+
+
+def _unique_row_ids(row_ids: torch.Tensor, rows: int) -> torch.Tensor:
+    """The sorted unique ids of a ``row_sparse_pull``; ``ValueError`` for one outside ``[0, rows)`` (one host
+    synchronisation for a GPU tensor: the host needs their count anyway)."""
+    ids = torch.unique(row_ids.reshape(-1).to(torch.int64))
+    if ids.numel() and (int(ids[0]) < 0 or int(ids[-1]) >= rows):
+        raise ValueError(f"row_sparse_pull: row ids must be in [0, {rows})")
+    return ids
+
+
+def _rsp_gather(table: torch.Tensor, ids: torch.Tensor) -> torch.Tensor:
+    """Rows ``ids`` (sorted, in range, on the table's device) of the dense ``[R, ...]`` ``table``."""
+    re = _row_elems(table.shape)
+    if not (ids.numel() and _rsp_kernel_rows(table, re) and table.is_contiguous() and table.data_ptr() % 16 == 0):
+        return table.index_select(0, ids)
+    from ..ops import _lib
+
+    ids = ids.contiguous()
+    out = torch.empty((ids.numel(),) + tuple(table.shape[1:]), dtype=table.dtype, device=table.device)
+    with torch.cuda.device(table.device):
+        _lib.check(_lib.lib().tony_kv_rsp_gather(out.data_ptr(), table.data_ptr(), ids.data_ptr(), ids.numel(), 4 * re,
+                                                 table.shape[0], None, None, _lib.stream_ptr(table.device)),
+                   "tony_kv_rsp_gather")
+    return out
+
+
+def _rsp_merge(vals: List[RowSparse], device=None, dtype=None) -> RowSparse:
+    """The ordered merge of row-sparse values (module docstring) on ``device`` (the first value's by default)."""
+    first = vals[0]
+    device = first.data.device if device is None else torch.device(device)
+    dtype = first.data.dtype if dtype is None else dtype
+    vals = [v if (v.data.device == device and v.data.dtype == dtype) else
+            RowSparse(v.indices.to(device), v.data.to(device, dtype), v.shape, _checked=True) for v in vals]
+    for v in vals[1:]:
+        if v.shape != first.shape:
+            raise ValueError(f"row-sparse values of shapes {first.shape} and {v.shape} cannot be merged")
+    if len(vals) == 1:
+        return vals[0]
+    union = torch.unique(torch.cat([v.indices for v in vals]))
+    re, nu = _row_elems(first.shape), union.numel()
+    if nu and _rsp_kernel_rows(vals[0].data, re) and len(vals) <= _MAX_KV_WORKERS:
+        import ctypes
+
+        from ..ops import _lib
+
+        srcs = [(_aligned16(v.indices), _aligned16(v.data)) for v in vals]
+        out = torch.empty((nu,) + first.shape[1:], dtype=torch.float32, device=device)
+        arr = ctypes.c_int64 * len(vals)
+        with torch.cuda.device(device):
+            _lib.check(_lib.lib().tony_kv_rsp_merge(
+                out.data_ptr(), union.data_ptr(), nu, arr(*[i.data_ptr() if i.numel() else 0 for i, _ in srcs]),
+                arr(*[d.data_ptr() if d.numel() else 0 for _, d in srcs]), arr(*[i.numel() for i, _ in srcs]),
+                len(vals), re, _lib.stream_ptr(device)), "tony_kv_rsp_merge")
+        return RowSparse(union, out, first.shape, _checked=True)
+    acc = torch.zeros((nu,) + first.shape[1:], dtype=torch.float32, device=device)
+    have = torch.zeros(nu, dtype=torch.bool, device=device)
+    for v in vals:
+        if not v.nnz:
+            continue
+        pos = torch.searchsorted(union, v.indices)
+        d = v.data.float()
+        seen = have.index_select(0, pos).view((-1,) + (1,) * (d.dim() - 1))
+        acc.index_copy_(0, pos, torch.where(seen, acc.index_select(0, pos) + d, d))
+        have.index_fill_(0, pos, True)
+    return RowSparse(union, acc.to(dtype), first.shape, _checked=True)
+
+
+def _rsp_apply(opt: Optional["Optimizer"], kid: int, weight: torch.Tensor, merged: RowSparse) -> None:
+    """A merged row-sparse push into the dense ``weight`` [R, ...] (module docstring)."""
+    merged = _rsp_merge([merged], weight.device)
+    if opt is None:
+        weight.zero_()
+        if merged.nnz:
+            weight.index_copy_(0, merged.indices, merged.data.to(weight.dtype))
+        return
+    opt.update_rows(kid, weight, merged.indices, merged.data)
+
+
 class _KeyIds:
     def __init__(self):
         self.ids: Dict[object, int] = {}
@@ -272,6 +498,7 @@ class KVStore:
         self._store: Dict[int, torch.Tensor] = {}
         self._opt: Optional[Optimizer] = None
         self._key = _KeyIds()
+        self._sparse: Dict[int, tuple] = {}  # sparse keys (init with a RowSparse) -> their dense shape
 
     @property
     def rank(self) -> int:
@@ -288,13 +515,70 @@ class KVStore:
 
     def init(self, key, value) -> None:
         for k, v in zip(*self._keys_vals(key, value)):
-            self._store[self._key(k)] = _as_list(v)[0].detach().clone()
+            self._store[self._key(k)] = self._init_value(self._key(k), v)
+
+    def _init_value(self, kid: int, v) -> torch.Tensor:
+        """The dense tensor a key starts from; a ``RowSparse`` value makes the key a sparse key."""
+        v = _as_list(v)[0]
+        if isinstance(v, RowSparse):
+            self._sparse[kid] = v.shape
+            return v.to_dense()
+        return v.detach().clone()
+
+    def _sparse_push(self, kid: int, vals: list) -> bool:
+        """Whether ``vals`` is a row-sparse push of a sparse key; ``TypeError`` when value and key kinds differ."""
+        rsp = [isinstance(v, RowSparse) for v in vals]
+        if kid in self._sparse:
+            if not all(rsp):
+                raise TypeError(f"key {kid} is a row-sparse key: push RowSparse values to it")
+            for v in vals:
+                if v.shape != self._sparse[kid]:
+                    raise ValueError(f"key {kid} has shape {self._sparse[kid]}, the pushed RowSparse {v.shape}")
+            return True
+        if any(rsp):
+            raise TypeError(f"key {kid} is a dense key: a RowSparse cannot be pushed to it")
+        return False
 
     def push(self, key, value, priority: int = 0) -> None:  # noqa: ARG002
         for k, v in zip(*self._keys_vals(key, value)):
             kid = self._key(k)
+            if self._sparse_push(kid, _as_list(v)):
+                self._apply_rsp(kid, _rsp_merge(_as_list(v)))
+                continue
             g = _merge(_as_list(v))
             self._apply(kid, g)
+
+    def _apply_rsp(self, kid: int, merged: "RowSparse") -> None:
+        if kid not in self._store:
+            raise KeyError(f"key {kid} was not initialised")
+        _rsp_apply(self._opt, kid, self._store[kid], merged)
+
+    def row_sparse_pull(self, key, out=None, row_ids=None, priority: int = 0) -> None:  # noqa: ARG002
+        """``out.indices`` <- the sorted unique ``row_ids``, ``out.data`` <- those rows of the stored value (module
+        docstring); ``out`` a ``RowSparse`` or a list of them per key, ``row_ids`` one tensor per ``out``."""
+        keys, outs = self._keys_vals(key, out)
+        rids = list(row_ids) if isinstance(key, (list, tuple)) else [row_ids]
+        for k, o, r in zip(keys, outs, rids):
+            kid = self._key(k)
+            os_ = _as_list(o)
+            rs = list(r) if isinstance(r, (list, tuple)) else [r] * len(os_)
+            for dst, ids in zip(os_, rs):
+                if not isinstance(dst, RowSparse):
+                    raise TypeError("row_sparse_pull fills RowSparse values")
+                shape = self._rsp_shape(kid, dst)
+                ids = _unique_row_ids(ids, shape[0])
+                dev = dst.data.device
+                rows = self._pull_rows(kid, ids, shape, dst.data.dtype, dev)
+                dst.indices, dst.data, dst.shape = ids.to(dev), rows.to(dev).view((ids.numel(),) + shape[1:]), shape
+
+    def _rsp_shape(self, kid: int, dst: "RowSparse") -> tuple:  # noqa: ARG002
+        if kid not in self._store:
+            raise KeyError(f"key {kid} was not initialised")
+        return tuple(self._store[kid].shape)
+
+    def _pull_rows(self, kid: int, ids: torch.Tensor, shape: tuple, dtype, device) -> torch.Tensor:  # noqa: ARG002
+        src = self._store[kid]
+        return _rsp_gather(src, ids.to(src.device))
 
     def _apply(self, kid: int, merged: torch.Tensor) -> None:
         if kid not in self._store:
@@ -307,6 +591,8 @@ class KVStore:
     def pull(self, key, out=None, priority: int = 0, ignore_sparse: bool = True):  # noqa: ARG002
         keys, outs = self._keys_vals(key, out)
         for k, o in zip(keys, outs):
+            if ignore_sparse and self._key(k) in self._sparse:
+                continue
             src = self._store[self._key(k)]
             for t in _as_list(o):
                 t.copy_(src.to(t.device))
@@ -551,6 +837,31 @@ class _KvPlane:
         buf.record_stream(main)
         return buf, ev
 
+    def take_rsp(self, kid: int, w: int, nnz: int, dtype: torch.dtype, row_elems: int):
+        """Server: worker w's row-sparse push of kid -- ``nnz`` rows, then their int64 ids, in the worker's row of
+        the window (two flagged copies on the key's push flag) -- as new tensors, and the event after their read;
+        waited for and read on the worker's side stream like ``take``."""
+        _, nbytes, row_off, _, slot = self.keys[kid]
+        side = self._side.get(w)
+        if side is None:
+            side = self._side[w] = torch.cuda.Stream(self.device)
+        main = torch.cuda.current_stream(self.device)
+        with torch.cuda.stream(side):
+            rows = torch.empty(nnz * row_elems, dtype=dtype, device=self.device)
+            ids = torch.empty(nnz, dtype=torch.int64, device=self.device)
+            rb = rows.numel() * rows.element_size()
+            blocks = self.L.tony_kv_copy_blocks(rb) + self.L.tony_kv_copy_blocks(8 * nnz)
+            n = self._arrived[(kid, w)] = self._arrived.get((kid, w), 0) + blocks
+            self.wait(_push_flag(slot, w), n)
+            src = self.base + row_off + w * _pad16(nbytes)
+            self.copy(rows.data_ptr(), src, rb)
+            self.copy(ids.data_ptr(), src + rb, 8 * nnz)
+            ev = torch.cuda.Event()
+            ev.record(side)
+        rows.record_stream(main)
+        ids.record_stream(main)
+        return ids, rows, ev
+
     def decode(self, dst: int, src: int, numel: int, thr: float) -> None:
         """``copy`` for a row of 2-bit words: ``numel`` fp32 values decoded out of this rank's window, skipped on
         the device like the copy when a wait of this window timed out."""
@@ -655,8 +966,31 @@ class _Server:
         self.sends = []
         self.applied = 0
         self.round: Dict[int, list] = {}  # kid -> [(worker, arrival, payload, event)] of the open round
+        self.rsp: Dict[int, tuple] = {}  # sparse keys -> (rows R, elements of a row)
 
-    def _reply(self, kid: int, worker: int, via_plane: bool = False) -> None:
+    def _reply_rows(self, kid: int, worker: int, via_plane: bool, ids: torch.Tensor) -> None:
+        """The answer to a row_sparse_pull: rows ``ids`` of the value, gathered straight into the worker's landing
+        area and counted on its reply flag, or over gloo."""
+        rows, re = self.rsp[kid]
+        table = self.values[kid].view(rows, re)
+        if via_plane:
+            from ..ops import _lib
+
+            srv, _, _, land_off, slot = self.plane.keys[kid]
+            ids = ids.to(self.plane.device)
+            with torch.cuda.device(self.plane.device):
+                _lib.check(self.plane.L.tony_kv_rsp_gather(
+                    self.plane.peer[worker] + land_off, table.data_ptr(), ids.data_ptr(), ids.numel(),
+                    re * table.element_size(), rows, self.plane.peer_win[worker] + _reply_flag(self.topo, srv, slot),
+                    None, _lib.stream_ptr(self.plane.device)), "tony_kv_rsp_gather")
+            return
+        self.sends.append(dist.isend(table.index_select(0, ids.to(table.device)).cpu().contiguous(), worker,
+                                     tag=TAG_REPLY))
+
+    def _reply(self, kid: int, worker: int, via_plane: bool = False, ids: Optional[torch.Tensor] = None) -> None:
+        if ids is not None:
+            self._reply_rows(kid, worker, via_plane, ids)
+            return
         if via_plane:  # the value into the worker's landing area, counted on the worker's reply flag
             srv, nbytes, _, land_off, slot = self.plane.keys[kid]
             v = self.values[kid].contiguous()
@@ -670,6 +1004,13 @@ class _Server:
         every plane push's row read (device events: the host never waits for a payload)."""
         v = self.values[kid]
         merged = None
+        if kid in self.rsp:  # row-sparse pushes: the ordered merge of the module docstring
+            vals = []
+            for _, _, b, ev in sorted(self.round.pop(kid), key=lambda e: (e[0], e[1])):
+                if ev is not None:
+                    torch.cuda.current_stream(v.device).wait_event(ev)
+                vals.append(b)
+            return _rsp_merge(vals, v.device)
         for _, _, b, ev in sorted(self.round.pop(kid), key=lambda e: (e[0], e[1])):
             if ev is not None:
                 torch.cuda.current_stream(v.device).wait_event(ev)
@@ -679,17 +1020,70 @@ class _Server:
 
     def _finish_round(self, kid: int) -> None:
         merged = self._merge_round(kid)
-        if self.opt is not None:
+        if kid in self.rsp:
+            _rsp_apply(self.opt, kid, self.values[kid].view(self.rsp[kid][0], -1), merged)
+        elif self.opt is not None:
             self.opt.update(kid, self.values[kid], merged)
         else:
             self.values[kid].copy_(merged)
         self.applied += 1
         self.pushed[kid] = set()
-        for w, via in self.deferred.pop(kid, []):
-            self._reply(kid, w, via)
+        for w, via, ids in self.deferred.pop(kid, []):
+            self._reply(kid, w, via, ids)
+
+    def _rsp_request(self, worker: int, hdr: List[int], buf):
+        """A row-sparse request: its payload received, a pull answered (or deferred).  Returns None when it is
+        dealt with or parked, else ``(op, payload, event)`` for ``handle`` to carry on with: an ``OP_INIT`` with the
+        dense value or an ``OP_PUSH`` with the pushed ``RowSparse``."""
+        op, kid, numel, dcode = hdr
+        dt = _DTYPES[dcode]
+        if buf is None:
+            if op == OP_INIT_RSP:
+                dense, rows = torch.empty(numel, dtype=dt), torch.empty(1, dtype=torch.int64)
+                dist.recv(dense, worker, tag=TAG_DATA)
+                dist.recv(rows, worker, tag=TAG_DATA)
+                buf = (dense, int(rows[0]))
+            elif op == OP_PUSH_RSP and numel:
+                meta = torch.empty(numel + 1, dtype=torch.int64)  # the ids, then the elements of a row
+                dist.recv(meta, worker, tag=TAG_DATA)
+                data = torch.empty(numel * int(meta[-1]), dtype=dt)
+                dist.recv(data, worker, tag=TAG_DATA)
+                buf = (meta[:-1].clone(), data)
+            elif op in (OP_PULL_RSP, OP_PULL_RSPX):
+                buf = torch.empty(numel, dtype=torch.int64)
+                dist.recv(buf, worker, tag=TAG_DATA)
+        if op == OP_INIT_RSP:
+            dense, rows = buf
+            self.rsp[kid] = (rows, dense.numel() // max(1, rows))
+            return OP_INIT, dense, None
+        if kid not in self.values:  # raced ahead of worker 0's INIT: replayed once the key exists (see handle)
+            self.early.setdefault(kid, []).append((worker, hdr, buf))
+            return None
+        rows, re = self.rsp[kid]
+        if op in (OP_PULL_RSP, OP_PULL_RSPX):
+            via = op == OP_PULL_RSPX
+            if self.sync and worker in self.pushed.get(kid, ()):
+                self.deferred.setdefault(kid, []).append((worker, via, buf))
+            else:
+                self._reply(kid, worker, via, buf)
+            return None
+        ev = None
+        if op == OP_PUSH_RSPX and numel:
+            ids, data, ev = self.plane.take_rsp(kid, worker - self.topo.num_servers, numel, dt, re)
+        elif numel:
+            ids, data = buf
+        else:
+            ids, data = torch.empty(0, dtype=torch.int64), torch.empty(0, dtype=dt)
+        return OP_PUSH, RowSparse(ids, data.view(numel, re), (rows, re), _checked=True), ev
 
     def handle(self, worker: int, hdr: List[int], buf: Optional[torch.Tensor] = None) -> bool:
         op, kid, numel, dcode = hdr
+        ev_rsp = None
+        if op >= OP_INIT_RSP:
+            got = self._rsp_request(worker, hdr, buf)
+            if got is None:
+                return True
+            op, buf, ev_rsp = got
         if op in (OP_INIT, OP_PUSH, OP_OPT, OP_GC) and buf is None:
             buf = torch.empty(numel, dtype=_DTYPES[dcode])
             dist.recv(buf, worker, tag=TAG_DATA)
@@ -714,7 +1108,7 @@ class _Server:
             # the worker does not rewrite that row before its next pull (DistKVStore._unread)
             self.early.setdefault(kid, []).append((worker, hdr, buf))
             return True
-        ev = None
+        ev = ev_rsp
         if op == OP_PUSH_X:  # the payload is in this worker's receive row of the window: take it now
             buf, ev = self.plane.take(kid, worker - self.topo.num_servers, numel, _DTYPES[dcode])
             op = OP_PUSH
@@ -734,6 +1128,7 @@ class _Server:
             if op == OP_INIT:
                 if self.plane is not None and self.plane.add_key(kid, buf.numel() * buf.element_size()):
                     buf = buf.to(self.plane.device)  # the key's value lives on the server's GPU
+
                 self.values[kid] = buf
                 self.pushed[kid] = set()
                 for w, h, b in self.early.pop(kid, []):
@@ -751,7 +1146,7 @@ class _Server:
                     self._finish_round(kid)
         elif op == OP_PULL:
             if self.sync and worker in self.pushed.get(kid, ()):
-                self.deferred.setdefault(kid, []).append((worker, via))
+                self.deferred.setdefault(kid, []).append((worker, via, None))
             else:
                 self._reply(kid, worker, via)
         elif op == OP_STOP:
@@ -817,6 +1212,10 @@ class DistKVStore(KVStore):
         self._res = _Residuals()
         self._pushed = False
         self.compressed_ops = [0, 0]  # 2-bit pushes whose words went over the GPU plane / over gloo (tests)
+        # row-sparse pushes on the plane / over gloo, row_sparse_pulls on the plane / over gloo (tests); a push or
+        # pull of no rows moves no payload and is counted nowhere
+        self.sparse_ops = [0, 0, 0, 0]
+        self._rsp_dtype: Dict[int, torch.dtype] = {}  # sparse keys -> the dtype of their value
         self._closed = False
 
     @property
@@ -838,12 +1237,19 @@ class DistKVStore(KVStore):
     def init(self, key, value) -> None:
         for k, v in zip(*self._keys_vals(key, value)):
             kid = self._key(k)
-            t = _as_list(v)[0].detach()
+            t = _as_list(v)[0]
+            sparse = isinstance(t, RowSparse)
+            if sparse:  # a sparse key: the servers hold its dense value and learn its row count
+                self._sparse[kid], self._rsp_dtype[kid] = t.shape, t.data.dtype
+                t = t.to_dense()
+            t = t.detach()
             self._shapes[kid] = t.shape
             if self.plane is not None:
                 self.plane.add_key(kid, t.numel() * t.element_size())
             if self.rank == 0:
-                self._send(OP_INIT, kid, t.reshape(-1).cpu().contiguous())
+                srv = self._send(OP_INIT_RSP if sparse else OP_INIT, kid, t.reshape(-1).cpu().contiguous())
+                if sparse:
+                    dist.send(torch.tensor([t.shape[0]], dtype=torch.int64), srv, tag=TAG_DATA)
         self.barrier()
 
     def _on_plane(self, kid: int, t: torch.Tensor) -> bool:
@@ -852,6 +1258,10 @@ class DistKVStore(KVStore):
     def push(self, key, value, priority: int = 0) -> None:  # noqa: ARG002
         for k, v in zip(*self._keys_vals(key, value)):
             kid = self._key(k)
+            if self._sparse_push(kid, _as_list(v)):  # (never compressed, as in MXNet)
+                self._pushed = True
+                self._push_rsp(kid, _rsp_merge(_as_list(v)))
+                continue
             g = _merge(_as_list(v)).reshape(-1)
             self._pushed = True
             if self._gc is not None and g.dtype == torch.float32:
@@ -872,6 +1282,96 @@ class DistKVStore(KVStore):
                 self.plane_ops[0] += 1
                 continue
             self._send(OP_PUSH, kid, g.cpu().contiguous())
+
+    def _push_rsp(self, kid: int, m: RowSparse) -> None:
+        """A push of the merged row-sparse value ``m`` (module docstring)."""
+        srv = self.topo.server_of(kid)
+        nnz, re = m.nnz, _row_elems(m.shape)
+        row_bytes = re * m.data.element_size()
+        hdr = [kid, nnz, _dcode(m.data.dtype)]
+        if nnz == 0:  # the header only: the server counts this worker's (empty) part of the round
+            dist.send(torch.tensor([OP_PUSH_RSP] + hdr, dtype=torch.int64), srv, tag=TAG_HDR)
+            return
+        if (self._on_plane(kid, m.data) and kid not in self._unread and row_bytes % 16 == 0
+                and nnz * row_bytes + _pad16(8 * nnz) <= _pad16(self.plane.keys[kid][1])):
+            _, nbytes, row_off, _, slot = self.plane.keys[kid]
+            rows = _aligned16(m.data.to(self.plane.device))
+            ids = _aligned16(m.indices.to(self.plane.device))
+            # the rows, then the ids behind them, into this worker's row of the server's window: two copies
+            # counted on the key's push flag there (the server computes both counts from nnz)
+            base = self.plane.peer[srv] + row_off + self.rank * _pad16(nbytes)
+            flag = self.plane.peer_win[srv] + _push_flag(slot, self.rank)
+            self.plane.send(base, rows.data_ptr(), nnz * row_bytes, flag)
+            self.plane.send(base + nnz * row_bytes, ids.data_ptr(), 8 * nnz, flag)
+            dist.send(torch.tensor([OP_PUSH_RSPX] + hdr, dtype=torch.int64), srv, tag=TAG_HDR)
+            self._unread.add(kid)
+            self.plane_ops[0] += 1
+            self.sparse_ops[0] += 1
+            return
+        # off the plane, too many rows for the window row, a re-push before a pull or a CPU value: over gloo
+        dist.send(torch.tensor([OP_PUSH_RSP] + hdr, dtype=torch.int64), srv, tag=TAG_HDR)
+        dist.send(torch.cat([m.indices.cpu(), torch.tensor([re], dtype=torch.int64)]), srv, tag=TAG_DATA)
+        dist.send(m.data.reshape(-1).cpu().contiguous(), srv, tag=TAG_DATA)
+        self.sparse_ops[1] += 1
+
+    def _rsp_shape(self, kid: int, dst: RowSparse) -> tuple:  # noqa: ARG002
+        if kid not in self._sparse:
+            raise TypeError(f"row_sparse_pull: key {kid} is not a row-sparse key of this store")
+        return self._sparse[kid]
+
+    def _pull_rows(self, kid: int, ids: torch.Tensor, shape: tuple, dtype, device) -> torch.Tensor:  # noqa: ARG002
+        """Rows ``ids`` (sorted, unique, in range) of a sparse key from its server.  The ids go over gloo with the
+        header (8 B per row against the row's bytes; the host needs their count anyway: one synchronisation per
+        call); on the plane the server gathers the rows into this worker's landing area."""
+        nnz, re, kdt = ids.numel(), _row_elems(shape), self._rsp_dtype[kid]
+        if nnz == 0:
+            return torch.empty((0,) + shape[1:], dtype=kdt, device=device)
+        row_bytes = re * torch.empty((), dtype=kdt).element_size()
+        hdr = torch.tensor([0, kid, nnz, _dcode(kdt)], dtype=torch.int64)
+        cpu_ids = ids.cpu().contiguous()
+        if (self.plane is not None and kid in self.plane.keys and device.type == "cuda" and kdt == torch.float32
+                and row_bytes % 16 == 0):
+            hdr[0] = OP_PULL_RSPX
+            blocks = self.plane.L.tony_kv_rsp_gather_blocks(nnz, row_bytes)
+            buf = self._plane_fetch(kid, hdr, cpu_ids, blocks, nnz * row_bytes, nnz * re, kdt)
+            self.sparse_ops[2] += 1
+        else:
+            hdr[0] = OP_PULL_RSP
+            srv = self.topo.server_of(kid)
+            dist.send(hdr, srv, tag=TAG_HDR)
+            dist.send(cpu_ids, srv, tag=TAG_DATA)
+            buf = torch.empty(nnz * re, dtype=kdt)
+            dist.recv(buf, srv, tag=TAG_REPLY)
+            self._unread.discard(kid)
+            self.sparse_ops[3] += 1
+        return buf.view((nnz,) + shape[1:])
+
+    def _plane_fetch(self, kid: int, hdr: torch.Tensor, ids: Optional[torch.Tensor], blocks: int, nbytes: int,
+                     numel: int, dtype: torch.dtype) -> torch.Tensor:
+        """Ask the key's server (``hdr``, then ``ids`` if any) for a reply into this worker's landing area and
+        copy its ``nbytes`` out behind a device wait for the ``blocks`` counts the reply adds to the reply flag."""
+        srv, _, _, land_off, slot = self.plane.keys[kid]
+        prev = self._landed.pop(kid, None)
+        if prev is not None and kid not in self._unread:
+            # no push since the last pull: nothing orders the server's next reply store after that
+            # pull's copy-out (a push would -- the server answers only after reading it, and the push
+            # copy queues behind the copy-out); wait for the copy-out before asking again
+            prev.synchronize()
+        dist.send(hdr, srv, tag=TAG_HDR)
+        if ids is not None:
+            dist.send(ids, srv, tag=TAG_DATA)
+        # the reply lands in this worker's landing area, counted on its reply flag: this stream waits
+        # for it on the device, then copies it out -- the host moves on at once
+        n = self._replies[kid] = self._replies.get(kid, 0) + blocks
+        self.plane.wait(_reply_flag(self.topo, srv, slot), n)
+        buf = torch.empty(numel, dtype=dtype, device=self.plane.device)
+        self.plane.copy(buf.data_ptr(), self.plane.base + land_off, nbytes)
+        ev = torch.cuda.Event()
+        ev.record(torch.cuda.current_stream(self.plane.device))
+        self._landed[kid] = ev
+        self._unread.discard(kid)  # the server answered: it consumed this worker's earlier rows
+        self.plane_ops[1] += 1
+        return buf
 
     def _push_2bit(self, kid: int, g: torch.Tensor) -> None:
         """A push of the merged flat fp32 gradient with 2-bit compression on (module docstring)."""
@@ -913,27 +1413,13 @@ class DistKVStore(KVStore):
         keys, outs = self._keys_vals(key, out)
         for k, o in zip(keys, outs):
             kid = self._key(k)
+            if ignore_sparse and kid in self._sparse:
+                continue
             first = _as_list(o)[0]
             if self._on_plane(kid, first):
-                srv, nbytes, _, land_off, slot = self.plane.keys[kid]
-                prev = self._landed.pop(kid, None)
-                if prev is not None and kid not in self._unread:
-                    # no push since the last pull: nothing orders the server's next reply store after that
-                    # pull's copy-out (a push would -- the server answers only after reading it, and the push
-                    # copy queues behind the copy-out); wait for the copy-out before asking again
-                    prev.synchronize()
-                dist.send(torch.tensor([OP_PULL_X, kid, 0, 0], dtype=torch.int64), srv, tag=TAG_HDR)
-                # the reply lands in this worker's landing area, counted on its reply flag: this stream waits
-                # for it on the device, then copies it out -- the host moves on at once
-                n = self._replies[kid] = self._replies.get(kid, 0) + self.plane.L.tony_kv_copy_blocks(nbytes)
-                self.plane.wait(_reply_flag(self.topo, srv, slot), n)
-                buf = torch.empty(first.numel(), dtype=first.dtype, device=self.plane.device)
-                self.plane.copy(buf.data_ptr(), self.plane.base + land_off, nbytes)
-                ev = torch.cuda.Event()
-                ev.record(torch.cuda.current_stream(self.plane.device))
-                self._landed[kid] = ev
-                self._unread.discard(kid)  # the server answered: it consumed this worker's earlier rows
-                self.plane_ops[1] += 1
+                nbytes = self.plane.keys[kid][1]
+                buf = self._plane_fetch(kid, torch.tensor([OP_PULL_X, kid, 0, 0], dtype=torch.int64), None,
+                                        self.plane.L.tony_kv_copy_blocks(nbytes), nbytes, first.numel(), first.dtype)
             else:
                 srv = self._send(OP_PULL, kid)
                 buf = torch.empty(first.numel(), dtype=first.dtype)
@@ -1001,12 +1487,16 @@ class DeviceSyncKVStore(KVStore):
 
     def init(self, key, value) -> None:
         for k, v in zip(*self._keys_vals(key, value)):
-            t = _as_list(v)[0].detach().clone()
+            t = self._init_value(self._key(k), v)
             dist.broadcast(t, 0, group=self.group)
             self._store[self._key(k)] = t
 
     def push(self, key, value, priority: int = 0) -> None:  # noqa: ARG002
         for k, v in zip(*self._keys_vals(key, value)):
+            if self._sparse_push(self._key(k), _as_list(v)):  # (never compressed, as in MXNet)
+                self._pushed = True
+                self._apply_rsp(self._key(k), self._allgather_rsp(_rsp_merge(_as_list(v))))
+                continue
             g = _merge(_as_list(v))
             self._pushed = True
             if self._gc is not None and g.dtype == torch.float32:
@@ -1014,6 +1504,27 @@ class DeviceSyncKVStore(KVStore):
                 continue
             dist.all_reduce(g, group=self.group)
             self._apply(self._key(k), g)
+
+    def _allgather_rsp(self, m: RowSparse) -> RowSparse:
+        """The workers' row-sparse pushes merged in rank order, identically on every worker: the row counts
+        all-gathered (one host synchronisation), then the ids and rows padded to the largest."""
+        nw, dev, nnz = self.num_workers, m.data.device, m.nnz
+        counts = torch.zeros(nw, 1, dtype=torch.int64, device=dev)
+        dist.all_gather(list(counts.unbind(0)), torch.tensor([nnz], dtype=torch.int64, device=dev), group=self.group)
+        counts = counts.reshape(-1).tolist()
+        most, re = max(counts), _row_elems(m.shape)
+        if most == 0:
+            return m
+        ids = torch.zeros(most, dtype=torch.int64, device=dev)
+        rows = torch.zeros(most * re, dtype=m.data.dtype, device=dev)
+        ids[:nnz].copy_(m.indices)
+        rows[:nnz * re].copy_(m.data.reshape(-1))
+        all_ids = torch.empty(nw, most, dtype=torch.int64, device=dev)
+        all_rows = torch.empty(nw, most * re, dtype=m.data.dtype, device=dev)
+        dist.all_gather(list(all_ids.unbind(0)), ids, group=self.group)
+        dist.all_gather(list(all_rows.unbind(0)), rows, group=self.group)
+        return _rsp_merge([RowSparse(all_ids[r, :n], all_rows[r, :n * re].view((n,) + m.shape[1:]), m.shape,
+                                     _checked=True) for r, n in enumerate(counts)])
 
     def _allgather_2bit(self, kid: int, g: torch.Tensor) -> torch.Tensor:
         """The workers' 2-bit pushes of flat fp32 ``g``: the words all-gathered, the decoded values summed in
