@@ -34,13 +34,19 @@ def main(argv=None) -> int:
                     help="apply Adam with the fused HIP kernel over the flat parameter buffer (GPU ranks)")
     ap.add_argument("--clip-norm", type=float, default=0.0,
                     help="clip the averaged gradient by its global norm (0: off; needs --fused)")
+    ap.add_argument("--adasum", action="store_true",
+                    help="combine the gradients with op=hvd.Adasum instead of averaging them; the learning rate is "
+                         "then NOT scaled by size() (needs a power-of-two number of ranks)")
     a = ap.parse_args(argv)
     hvd.init()
     dev = hvd.device()
     log(f"hvd rank {hvd.rank()}/{hvd.size()} local {hvd.local_rank()}/{hvd.local_size()} on {dev}")
     model = mnist_model("hvd_cnn", seed=hvd.rank()).to(dev)
-    opt = torch.optim.Adam(model.parameters(), lr=a.lr * hvd.size())
-    opt = hvd.DistributedOptimizer(opt, named_parameters=model.named_parameters(),
+    op = hvd.Adasum if a.adasum else hvd.Average
+    lr = a.lr if a.adasum else a.lr * hvd.size()
+    log(f"gradient reduction op={op} lr={lr:g}")
+    opt = torch.optim.Adam(model.parameters(), lr=lr)
+    opt = hvd.DistributedOptimizer(opt, named_parameters=model.named_parameters(), op=op,
                                    fused=True if a.fused else None,
                                    clip_norm=a.clip_norm if a.clip_norm > 0 else None)
     hvd.broadcast_parameters(model.state_dict(), root_rank=0)
@@ -59,7 +65,7 @@ def main(argv=None) -> int:
         ckpt = CheckpointManager(os.path.join(working_dir(), "hvd_mnist"), rank=0)
         ckpt.save(a.steps, {"model": model.state_dict()}, force=True)
         ckpt.wait()
-        metric(first_loss=losses[0], avg_last_loss=avg_last, size=hvd.size())
+        metric(first_loss=losses[0], avg_last_loss=avg_last, size=hvd.size(), op=str(op))
     log(f"loss {losses[0]:.4f} -> {losses[-1]:.4f} (avg over ranks {avg_last:.4f})")
     hvd.shutdown()
     return 0

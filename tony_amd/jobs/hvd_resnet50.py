@@ -40,6 +40,9 @@ def main(argv=None) -> int:
                     help="lars: linear learning-rate warm-up over this many steps (0 with --decay-steps 0: constant)")
     ap.add_argument("--decay-steps", type=int, default=0,
                     help="lars: polynomial (power 2) decay to 0 at this step, counted from step 0")
+    ap.add_argument("--adasum", action="store_true",
+                    help="combine the gradients with op=hvd.Adasum instead of averaging them; the learning rate is "
+                         "then NOT scaled by size() (needs a power-of-two number of ranks)")
     a = ap.parse_args(argv)
     hvd.init()
     dev = hvd.device()
@@ -48,10 +51,13 @@ def main(argv=None) -> int:
     if on_gpu:
         torch.backends.cudnn.benchmark = True
     model = cast_model(resnet50(fused=on_gpu), dtype, dev).to(memory_format=torch.channels_last)
-    opt = torch.optim.SGD(model.parameters(), lr=0.1 * hvd.size(), momentum=0.9, weight_decay=5e-5)
-    base_lr = 0.1 * hvd.size()
+    op = hvd.Adasum if a.adasum else hvd.Average
+    base_lr = 0.1 if a.adasum else 0.1 * hvd.size()  # Adasum: the point of the operator is not to retune by size()
+    log(f"gradient reduction op={op} lr={base_lr:g}")
+    opt = torch.optim.SGD(model.parameters(), lr=base_lr, momentum=0.9, weight_decay=5e-5)
     lars_kw = dict(fused=True, lars_coef=a.trust_coef) if a.optimizer == "lars" else {}
-    opt = hvd.DistributedOptimizer(opt, named_parameters=model.named_parameters(), bucket_mb=a.bucket_mb, **lars_kw)
+    opt = hvd.DistributedOptimizer(opt, named_parameters=model.named_parameters(), bucket_mb=a.bucket_mb, op=op,
+                                   **lars_kw)
     scheduled = a.optimizer == "lars" and (a.warmup_steps > 0 or a.decay_steps > 0)
     x, y = synthetic_images(a.batch_size, a.image_size, 1000, dev, dtype, seed=hvd.rank())
     tp = Throughput(dev)
@@ -72,7 +78,7 @@ def main(argv=None) -> int:
     if hvd.rank() == 0:
         extra = dict(optimizer="lars", lr=opt.param_groups[0]["lr"]) if a.optimizer == "lars" else {}
         metric(model="resnet50", images_per_sec=rate, size=hvd.size(), batch_per_rank=a.batch_size,
-               loss=float(loss), **extra)
+               loss=float(loss), op=str(op), **extra)
     log(f"{rate:.1f} images/sec over {hvd.size()} ranks")
     hvd.shutdown()
     return 0

@@ -235,6 +235,12 @@ _SIGNATURES = {
                           ctypes.POINTER(c_int64), c_int, c_int64, c_void_p],
     "tony_kv_rsp_sgd": [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_int64, c_float, c_float, c_float,
                         c_float, c_int, c_float, c_void_p],
+    # Adasum of two flat gradient buffers (csrc/adasum.hip, ops/adasum.py): a, b, is_bf16, items, n_items, partials |
+    # partials, order, tstart, T, coef | dst, other, dst_is_a, is_bf16, items, n_items, coef
+    "tony_adasum_item_floats": [],
+    "tony_adasum_dots": [c_void_p, c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p],
+    "tony_adasum_coef": [c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p],
+    "tony_adasum_combine": [c_void_p, c_void_p, c_int, c_int, c_void_p, c_int, c_void_p, c_void_p],
     "tony_ps_max_buckets": [],
     "tony_ps_max_blocks": [],
     "tony_ps_land_entry_bytes": [],

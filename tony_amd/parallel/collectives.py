@@ -139,6 +139,43 @@ def all_reduce(t: torch.Tensor, op=None, group=None, async_op=False, average: bo
     return dist.all_reduce(t, op=op or dist.ReduceOp.SUM, group=group, async_op=async_op)
 
 
+def adasum_all_reduce_(t: torch.Tensor, plan, group=None) -> torch.Tensor:
+    """Adasum of ``t`` over the ranks of ``group``, in place, per tensor of ``plan`` (an ``ops.adasum.AdasumPlan`` of
+    ``t``'s layout; the contract is that module's docstring).  Recursive doubling: level d = 1, 2, 4, ... exchanges
+    the whole buffer with rank ``r ^ d`` into the plan's receive buffer and combines, the lower rank's side as ``a``;
+    both partners compute the same bits, so after the last level every rank holds the same result.
+
+    The exchange is one ``batch_isend_irecv`` per level.  On RCCL the current stream waits on its work object and the
+    host on nothing; a gloo group moves host memory only, so device tensors are staged through pinned buffers there
+    (the one-GPU rehearsal of the multi-rank tests), with the synchronisation that gloo's own collectives have."""
+    from ..ops import adasum
+
+    n = world(group)
+    adasum.check_world(n)
+    if n == 1:
+        return t
+    r = rank(group)
+    recv = plan.recv_buffer()
+    staged = t.is_cuda and _is_gloo(group)
+    d = 1
+    while d < n:
+        partner = r ^ d
+        peer = partner if group is None else dist.get_global_rank(group, partner)
+        if staged:
+            src, dst = plan.host_buffers()
+            src.copy_(t)
+        else:
+            src, dst = t, recv
+        ops = [dist.P2POp(dist.isend, src, peer, group), dist.P2POp(dist.irecv, dst, peer, group)]
+        for work in dist.batch_isend_irecv(ops):
+            work.wait()  # RCCL: the current stream waits, not the host
+        if staged:
+            recv.copy_(dst)
+        adasum.combine_(t, recv, r < partner, plan)
+        d <<= 1
+    return t
+
+
 def broadcast(t: torch.Tensor, src: int, group=None, async_op=False):
     if world(group) == 1:
         return None

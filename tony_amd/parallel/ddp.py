@@ -40,7 +40,7 @@ class BucketedAllReduce:
     """Average ``flat.grad`` over ``group`` in buckets overlapped with backward."""
 
     def __init__(self, flat: FlatParams, bucket_mb: float = DEFAULT_BUCKET_MB, group=None, average: bool = True,
-                 compression: Optional[torch.dtype] = None, predivide: float = 1.0):
+                 compression: Optional[torch.dtype] = None, predivide: float = 1.0, reduce: str = "allreduce"):
         self.flat = flat
         # Horovod's gradient_predivide_factor f: scale by 1/f before a SUM, by f/size after
         self.predivide = float(predivide)
@@ -51,6 +51,23 @@ class BucketedAllReduce:
         self.average = average
         self.compression = compression
         self.buckets: List[Bucket] = make_buckets(flat, bucket_mb)
+        # reduce="adasum": every bucket's gradients are combined by Adasum (ops/adasum.py) instead of summed; buckets
+        # cover whole parameters, so each gets its own plan (its tensors' segments, a slot's zero padding with the
+        # slot before it: it adds nothing to the sums) and there is no division by the number of ranks
+        if reduce not in ("allreduce", "adasum"):
+            raise ValueError(f"reduce must be 'allreduce' or 'adasum', got {reduce!r}")
+        self.reduce = reduce
+        self.plans = None
+        if reduce == "adasum":
+            from ..ops.adasum import AdasumPlan, check_world
+            from .flat import build_segments
+
+            check_world(self.world)
+            if self.predivide != 1.0:
+                raise ValueError("gradient_predivide_factor does not apply to Adasum (nothing is divided by size)")
+            wire = compression if compression is not None else flat.grad.dtype
+            self.plans = [AdasumPlan(build_segments(flat, [(b.lo, b.hi)]), wire, flat.grad.device)
+                          for b in self.buckets]
         self.engine = GradBucketEngine(flat, self.buckets, self._launch)
         self.engine.auto_arm = self._arm
         self.enabled = True
@@ -85,6 +102,11 @@ class BucketedAllReduce:
         kernels and RCCL stays the A/B baseline; a fallback to RCCL is counted there."""
         g = self.flat.grad[b.lo:b.hi]
         wire = g.to(self.compression) if self.compression is not None and g.dtype != self.compression else g
+        if self.plans is not None:  # the level loop of Adasum on the wire copy, which is what gets combined
+            coll.adasum_all_reduce_(wire, self.plans[b.index], group=self.group)
+            if wire is not g:
+                g.copy_(wire)
+            return
         if self.predivide != 1.0:
             if wire is g:
                 wire = g.clone()

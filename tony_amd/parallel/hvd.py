@@ -148,7 +148,7 @@ def _reduce_op(op) -> Tuple[dist.ReduceOp, bool]:
     if op is None or op is Average:
         return dist.ReduceOp.SUM, True
     if op is Adasum:
-        raise NotImplementedError("Adasum is not supported; use Average or Sum")
+        return None, False  # no torch reduction: the level loop of parallel/collectives.py adasum_all_reduce_
     return {Sum: dist.ReduceOp.SUM, Min: dist.ReduceOp.MIN, Max: dist.ReduceOp.MAX,
             Product: dist.ReduceOp.PRODUCT}[op], False
 
@@ -164,13 +164,58 @@ class _Handle:
         self.work, self.out, self.post = work, out, post
 
 
+def _adasum_check(tensors) -> None:
+    """What ``op=Adasum`` asks of its arguments, raised where the operator is requested."""
+    from ..ops.adasum import check_world
+
+    for t in tensors:
+        if not t.is_floating_point():
+            raise TypeError(f"op=Adasum combines floating-point tensors, got {t.dtype}")
+    if len({(t.dtype, t.device) for t in tensors}) != 1:
+        raise TypeError("op=Adasum needs the tensors of a grouped call on one device and of one dtype")
+    check_world(_state["size"])
+
+
+def _adasum_(tensors) -> None:
+    """Adasum over the ranks of every tensor of the list, in place, each with its own coefficients: packed into one
+    buffer (ops/adasum.py ``AdasumPlan.packed``; the plan of a list of sizes is built once and kept), combined level by
+    level (parallel/collectives.py ``adasum_all_reduce_``), unpacked."""
+    if _state["size"] == 1:
+        return
+    from ..ops.adasum import AdasumPlan
+    from .collectives import adasum_all_reduce_
+
+    t0 = tensors[0]
+    key = (tuple(t.numel() for t in tensors), t0.dtype, str(t0.device))
+    plans = _state.setdefault("adasum_plans", {})
+    plan = plans.get(key)
+    if plan is None:
+        plan = plans[key] = AdasumPlan.packed(key[0], t0.dtype, t0.device)
+        plan.pack = torch.empty(plan.numel, dtype=t0.dtype, device=t0.device)
+    plan.pack.zero_()  # the padding: zero on both sides, it adds nothing to the sums (a NaN of an earlier call must go)
+    views = [plan.pack[off:off + t.numel()] for off, t in zip(plan.offsets, tensors)]
+    for v, t in zip(views, tensors):
+        v.copy_(t.reshape(-1))
+    adasum_all_reduce_(plan.pack, plan)
+    for v, t in zip(views, tensors):
+        t.copy_(v.view_as(t))
+
+
 def allreduce_async_(tensor: torch.Tensor, average=None, name=None, op=None, prescale_factor=1.0,
                      postscale_factor=1.0, process_set=None) -> int:  # noqa: ARG001
     _need_init()
     op = _resolve_op(average, op)
     top, div = _reduce_op(op)
+    if op is Adasum:
+        _adasum_check([tensor])
     if prescale_factor != 1.0:
         tensor.mul_(prescale_factor)
+    if op is Adasum:  # the work is done at issue: the handle is already complete
+        _adasum_([tensor])
+        h = _state["next_handle"]
+        _state["next_handle"] = h + 1
+        _state["handles"][h] = _Handle(None, tensor, postscale_factor)
+        return h
     work = dist.all_reduce(tensor, op=top, async_op=True) if _state["size"] > 1 else None
     scale = postscale_factor / (_state["size"] if div else 1)
     h = _state["next_handle"]
@@ -215,6 +260,21 @@ def grouped_allreduce(tensors: List[torch.Tensor], average=None, name=None, op=N
     """One fused collective over a list: pack into one buffer, reduce, unpack."""
     if not tensors:
         return []
+    if _resolve_op(average, op) is Adasum:
+        # one coefficient pair per tensor: the tensors are packed at 16-byte-aligned offsets with zero padding, one
+        # segment each (a plain torch.cat would leave the kernels' vector loads straddling two tensors)
+        _need_init()
+        _adasum_check(tensors)
+        pre, post = kw.get("prescale_factor", 1.0), kw.get("postscale_factor", 1.0)
+        out = [t.clone() for t in tensors]
+        if pre != 1.0:
+            for t in out:
+                t.mul_(pre)
+        _adasum_(out)
+        if post != 1.0:
+            for t in out:
+                t.mul_(post)
+        return out
     flat = torch.cat([t.reshape(-1) for t in tensors])
     allreduce_(flat, average, name, op, **kw)
     out, off = [], 0
@@ -376,8 +436,17 @@ class _DistributedOptimizer:
                              f"as AdamW's is), got torch.optim.{type(optimizer).__name__}")
         if lars_coef is not None and not isinstance(optimizer, torch.optim.SGD):
             raise ValueError(f"lars_coef needs a torch.optim.SGD, got torch.optim.{type(optimizer).__name__}")
-        if op not in (Average, Sum):
-            raise ValueError("DistributedOptimizer supports op=Average or op=Sum")
+        if op not in (Average, Sum, Adasum):
+            raise ValueError("DistributedOptimizer supports op=Average, op=Sum or op=Adasum")
+        if op is Adasum:
+            # the GRADIENTS are combined, before the step (Horovod's TensorFlow DistributedOptimizer; horovod.torch
+            # combines the optimizer's deltas instead): clip_norm, LARS and LAMB act on the combined gradient, the
+            # fused optimizers' grad_scale stays 1 and nothing is divided by size()
+            from ..ops.adasum import check_world
+
+            check_world(_state["size"])
+            if gradient_predivide_factor != 1.0:
+                raise ValueError("gradient_predivide_factor does not apply to op=Adasum")
         self.optimizer = optimizer
         self.backward_passes_per_step = int(backward_passes_per_step)
         params = [p for g in optimizer.param_groups for p in g["params"] if p.requires_grad]
@@ -402,7 +471,8 @@ class _DistributedOptimizer:
             if _state["size"] > 1:
                 dist.broadcast(flat.data, 0)
             red = BucketedAllReduce(flat, bucket_mb, average=(op is Average), compression=compression.dtype,
-                                    predivide=gradient_predivide_factor if op is Average else 1.0)
+                                    predivide=gradient_predivide_factor if op is Average else 1.0,
+                                    reduce="adasum" if op is Adasum else "allreduce")
             red.passes_per_reduce = self.backward_passes_per_step
             red.register_hooks()
             self.groups.append((flat, red))
@@ -636,7 +706,9 @@ def DistributedOptimizer(optimizer, named_parameters=None, compression=Compressi
     also takes a single-group Adam / AdamW / Adagrad / RMSprop over fp32 GPU parameters.  ``clip_norm`` (fused
     only) clips the averaged gradient by its global norm over all parameters before the apply.  ``lars_coef``
     (with a torch SGD) and ``lamb=True`` (with a torch AdamW), fused only, scale every parameter tensor's update by
-    its trust ratio (LARS / LAMB); ``adapt_filter(name, param)`` overrides which tensors are adapted."""
+    its trust ratio (LARS / LAMB); ``adapt_filter(name, param)`` overrides which tensors are adapted.
+    ``op=Adasum`` combines the gradients by Adasum, per parameter tensor, instead of averaging them (ops/adasum.py:
+    a power-of-two ``size()``, no ``gradient_predivide_factor``, and no learning rate scaled by ``size()``)."""
     return _DistributedOptimizer(optimizer, named_parameters, compression, backward_passes_per_step, op, **kw)
 
 
