@@ -43,6 +43,8 @@ def main(argv=None) -> int:
     ap.add_argument("--adasum", action="store_true",
                     help="combine the gradients with op=hvd.Adasum instead of averaging them; the learning rate is "
                          "then NOT scaled by size() (needs a power-of-two number of ranks)")
+    ap.add_argument("--sync-bn", action="store_true",
+                    help="BatchNorm statistics over all ranks' batches (tony_amd.models.syncbn.convert_sync_batchnorm)")
     a = ap.parse_args(argv)
     hvd.init()
     dev = hvd.device()
@@ -51,6 +53,11 @@ def main(argv=None) -> int:
     if on_gpu:
         torch.backends.cudnn.benchmark = True
     model = cast_model(resnet50(fused=on_gpu), dtype, dev).to(memory_format=torch.channels_last)
+    if a.sync_bn:
+        from tony_amd.models.syncbn import convert_sync_batchnorm
+
+        model = convert_sync_batchnorm(model)
+        log(f"sync_bn=True: BatchNorm statistics over the batches of {hvd.size()} ranks")
     op = hvd.Adasum if a.adasum else hvd.Average
     base_lr = 0.1 if a.adasum else 0.1 * hvd.size()  # Adasum: the point of the operator is not to retune by size()
     log(f"gradient reduction op={op} lr={base_lr:g}")
@@ -77,6 +84,8 @@ def main(argv=None) -> int:
     rate = float(hvd.allreduce(torch.tensor([tp.rate()]), op=hvd.Sum))
     if hvd.rank() == 0:
         extra = dict(optimizer="lars", lr=opt.param_groups[0]["lr"]) if a.optimizer == "lars" else {}
+        if a.sync_bn:
+            extra["sync_bn"] = True
         metric(model="resnet50", images_per_sec=rate, size=hvd.size(), batch_per_rank=a.batch_size,
                loss=float(loss), op=str(op), **extra)
     log(f"{rate:.1f} images/sec over {hvd.size()} ranks")

@@ -41,6 +41,8 @@ def main(argv=None) -> int:
                     help="train from the uint8 shards in DIR (tony_amd/data/images.py) instead of one synthetic batch")
     ap.add_argument("--eval-dir", default=None,
                     help="after training, top-1 / top-5 over the shards in DIR (central crop, eval mode)")
+    ap.add_argument("--sync-bn", action="store_true",
+                    help="BatchNorm statistics over all ranks' batches (tony_amd.models.syncbn.convert_sync_batchnorm)")
     a = ap.parse_args(argv)
     rank, world, _, dev = bootstrap.init_from_env()
     on_gpu = dev.type == "cuda"
@@ -48,6 +50,11 @@ def main(argv=None) -> int:
     if on_gpu:
         torch.backends.cudnn.benchmark = True
     model = cast_model(resnet50(fused=on_gpu), dtype, dev).to(memory_format=torch.channels_last)
+    if a.sync_bn:
+        from tony_amd.models.syncbn import convert_sync_batchnorm
+
+        model = convert_sync_batchnorm(model)
+        log(f"sync_bn=True: BatchNorm statistics over the batches of {world} ranks")
     ddp = DistributedDataParallel(model, bucket_mb=a.bucket_mb)
     opt = torch.optim.SGD(model.parameters(), lr=0.1 * world, momentum=0.9, weight_decay=5e-5)
     batches = None
@@ -81,7 +88,7 @@ def main(argv=None) -> int:
         t = torch.tensor([rate], dtype=torch.float64, device=dev)
         coll.all_reduce(t)
         rate = float(t.item())
-    extra = {}
+    extra = {"sync_bn": True} if a.sync_bn else {}
     if batches is not None:
         extra["input_wait_ms_per_step"] = (batches.wait_ms - wait0) / max(a.steps, 1)
         log(f"input: {extra['input_wait_ms_per_step']:.3f} ms per step blocked on the filler, "

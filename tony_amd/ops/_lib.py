@@ -241,6 +241,27 @@ _SIGNATURES = {
     "tony_adasum_dots": [c_void_p, c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p],
     "tony_adasum_coef": [c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p],
     "tony_adasum_combine": [c_void_p, c_void_p, c_int, c_int, c_void_p, c_int, c_void_p, c_void_p],
+    # synchronised BatchNorm (csrc/syncbn.hip, ops/syncbn.py): double partials [grid][2C] and their fold, the merges
+    # of the gathered packets into coefficient tables, and the row passes from a table.  M, C -> grid | x, M, C, ldx,
+    # is_f32, partials | partials, G, C, out, count | x, ldx, dy, lddy, y, ldy, M, C, is_f32, mean, invstd, gamma,
+    # beta, pb, relu, partials, out, dgamma, dbeta, accumulate | gathered, W, C, gamma, beta, pb, eps, momentum,
+    # save_mean, save_invstd, running_mean, running_var, coef, count_out | gathered, W, C, count, mean, invstd, gamma,
+    # beta, pb, tab | x, M, C, ldx, res, ldr, y, ldy, is_f32, coef, relu | x, ldx, dy, lddy, y, ldy, dres, lddr, dx,
+    # lddx, M, C, is_f32, tab, relu
+    "tony_syncbn_grid": [c_int64, c_int],
+    "tony_syncbn_stats": [c_void_p, c_int64, c_int, c_int64, c_int, c_void_p, c_void_p],
+    "tony_syncbn_fold": [c_void_p, c_int, c_int, c_void_p, c_int64, c_void_p],
+    "tony_syncbn_bwd_reduce": [c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_int64, c_int64, c_int, c_int,
+                               c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p,
+                               c_void_p, c_int, c_void_p],
+    "tony_syncbn_merge": [c_void_p, c_int, c_int, c_void_p, c_void_p, c_int, c_float, c_float, c_void_p, c_void_p,
+                          c_void_p, c_void_p, c_void_p, c_void_p, c_void_p],
+    "tony_syncbn_bwd_merge": [c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int,
+                              c_void_p, c_void_p],
+    "tony_syncbn_apply": [c_void_p, c_int64, c_int, c_int64, c_void_p, c_int64, c_void_p, c_int64, c_int, c_void_p,
+                          c_int, c_void_p],
+    "tony_syncbn_bwd_apply": [c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_int64, c_void_p,
+                              c_int64, c_int64, c_int, c_int, c_void_p, c_int, c_void_p],
     "tony_ps_max_buckets": [],
     "tony_ps_max_blocks": [],
     "tony_ps_land_entry_bytes": [],

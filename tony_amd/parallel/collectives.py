@@ -176,6 +176,28 @@ def adasum_all_reduce_(t: torch.Tensor, plan, group=None) -> torch.Tensor:
     return t
 
 
+def all_gather_packets(packet: torch.Tensor, group=None) -> torch.Tensor:
+    """``[world, n]`` <- every rank's contiguous 1-D ``packet`` of ``n`` elements, rank 0 first (the statistics
+    exchange of ops/syncbn.py: float64, at most 32 KB per rank, every rank reads the same gathered bytes).  RCCL:
+    one ``all_gather_into_tensor`` on the current stream.  A gloo group moves host memory only, so a device packet
+    is staged through pinned buffers there, as in ``adasum_all_reduce_``.  One rank, or no process group: a view."""
+    n = world(group)
+    if n == 1:
+        return packet.view(1, -1)
+    if not packet.is_cuda or not _is_gloo(group):
+        out = torch.empty((n, packet.numel()), dtype=packet.dtype, device=packet.device)
+        if packet.is_cuda:
+            dist.all_gather_into_tensor(out, packet, group=group)
+        else:
+            dist.all_gather(list(out.unbind(0)), packet, group=group)
+        return out
+    src = torch.empty(packet.shape, dtype=packet.dtype, pin_memory=True)
+    dst = torch.empty((n, packet.numel()), dtype=packet.dtype, pin_memory=True)
+    src.copy_(packet)  # (a device-to-host copy returns when the bytes are there)
+    dist.all_gather(list(dst.unbind(0)), src, group=group)
+    return dst.to(packet.device)
+
+
 def broadcast(t: torch.Tensor, src: int, group=None, async_op=False):
     if world(group) == 1:
         return None

@@ -6,7 +6,8 @@ use (EX/horovod-on-tony/tensorflow2_mnist.py:32-101, tensorflow2_keras_mnist.py:
 ``allreduce(_async)(_)``, ``allgather``, ``broadcast(_)``, ``alltoall``,
 ``broadcast_parameters``, ``broadcast_optimizer_state``, ``broadcast_object``,
 ``allgather_object``, ``DistributedOptimizer`` (fusion-buffer gradient averaging
-overlapped with backward), ``Compression``, ``join``, ``barrier``, ``shutdown``.
+overlapped with backward), ``Compression``, ``join``, ``barrier``, ``shutdown``,
+``SyncBatchNorm`` (BatchNorm statistics over all ranks' batches, ops/syncbn.py).
 
 Rendezvous: the horovod runtime exports ``HOROVOD_RANK/SIZE/LOCAL_RANK/...`` and
 ``HOROVOD_GLOO_RENDEZVOUS_ADDR/PORT`` (T/runtime/HorovodRuntime.java:318-349);
@@ -722,3 +723,14 @@ def shutdown() -> None:
 def allreduce_parameters_stats(params: Iterable[torch.Tensor]) -> List[torch.Tensor]:
     """MetricAverageCallback equivalent: average a list of scalars/tensors across ranks."""
     return [allreduce(torch.as_tensor(p, dtype=torch.float32)) for p in params]
+
+
+def __getattr__(name):
+    """``hvd.SyncBatchNorm(num_features, eps, momentum, affine, track_running_stats)``: BatchNorm whose training
+    statistics are those of all ranks' batches (ops/syncbn.py).  Resolved on first use: a job that never asks for it
+    imports none of it."""
+    if name == "SyncBatchNorm":
+        from ..ops.syncbn import SyncBatchNorm
+
+        return SyncBatchNorm
+    raise AttributeError(f"module {__name__!r} has no attribute {name!r}")
