@@ -33,6 +33,7 @@ def main(argv=None) -> int:
     ap.add_argument("--batch-size", type=int, default=1024)
     ap.add_argument("--epochs", type=int, default=2)
     ap.add_argument("--lr", type=float, default=0.1)
+    ap.add_argument("--optimizer", choices=["sgd", "nag", "adam", "adagrad", "rmsprop", "ftrl"], default="sgd")
     ap.add_argument("--gradient-compression", choices=["none", "2bit"], default="none")
     ap.add_argument("--gc-threshold", type=float, default=0.5)
     a = ap.parse_args(argv)
@@ -48,7 +49,10 @@ def main(argv=None) -> int:
     w, b = torch.zeros(1, 1), torch.zeros(1)
     store.init("fc_weight", w)
     store.init("fc_bias", b)
-    store.set_optimizer(kv.create_optimizer("sgd", learning_rate=a.lr, rescale_grad=1.0 / (a.batch_size * nw)))
+    store.set_optimizer(kv.create_optimizer(a.optimizer, learning_rate=a.lr, rescale_grad=1.0 / (a.batch_size * nw)))
+    extra = {} if a.optimizer == "sgd" else {"optimizer": a.optimizer}  # (the default's output stays as it was)
+    if extra:
+        log(f"worker {rank}/{nw}: optimizer {a.optimizer}, lr {a.lr}")
     if a.gradient_compression != "none":  # (the default takes none of the compression code)
         store.set_gradient_compression({"type": a.gradient_compression, "threshold": a.gc_threshold})
     mse = None
@@ -61,7 +65,7 @@ def main(argv=None) -> int:
             store.pull("fc_weight", out=w)
             store.pull("fc_bias", out=b)
         mse = float((((x @ w.t())[:, 0] + b - y) ** 2).mean())
-        metric(epoch=epoch, mse=mse, rank=rank)
+        metric(epoch=epoch, mse=mse, rank=rank, **extra)
     log(f"worker {rank}/{nw}: w={float(w):.3f} b={float(b):.3f} mse={mse:.5f}")
     store.close()
     return 0 if mse < 0.05 else 1

@@ -36,6 +36,8 @@ def main(argv=None) -> int:
     ap.add_argument("--batch-size", type=int, default=1024)
     ap.add_argument("--epochs", type=int, default=2)
     ap.add_argument("--lr", type=float, default=0.1)
+    ap.add_argument("--optimizer", choices=["sgd", "adam", "adagrad", "ftrl"], default="sgd",
+                    help="the servers' (lazy) update of the touched rows")
     ap.add_argument("--device", choices=["auto", "cpu", "cuda"], default="auto")
     a = ap.parse_args(argv)
     if kv.run_role():  # scheduler / server: serve until the workers are done
@@ -53,7 +55,10 @@ def main(argv=None) -> int:
     feats, labels, proj = feats[shard].to(dev), labels[shard].to(dev), proj.to(dev)
     shape = (F, D)
     store.init("table", kv.RowSparse(torch.zeros(0, dtype=torch.int64), torch.zeros(0, D), shape))  # all zero
-    store.set_optimizer(kv.create_optimizer("sgd", learning_rate=a.lr, rescale_grad=1.0 / nw))
+    store.set_optimizer(kv.create_optimizer(a.optimizer, learning_rate=a.lr, rescale_grad=1.0 / nw))
+    extra = {} if a.optimizer == "sgd" else {"optimizer": a.optimizer}  # (the default's output stays as it was)
+    if extra:
+        log(f"worker {rank}/{nw}: optimizer {a.optimizer}, lr {a.lr}")
     rows = kv.RowSparse(torch.zeros(0, dtype=torch.int64, device=dev), torch.zeros(0, D, device=dev), shape)
     rate = Throughput(dev)
     first = last = None
@@ -74,13 +79,13 @@ def main(argv=None) -> int:
             rate.add(fb.shape[0])
         last = total / max(1, seen)
         first = last if first is None else first
-        metric(epoch=epoch, loss=last, samples_per_s=rate.rate(), rank=rank)
+        metric(epoch=epoch, loss=last, samples_per_s=rate.rate(), rank=rank, **extra)
     store.barrier()  # every worker's last push is applied (its round closed, or its pull answered) before the read
     store.row_sparse_pull("table", out=rows, row_ids=feats[:1])
     table = torch.empty(shape, device=dev)
     store.pull("table", out=table, ignore_sparse=False)
     digest = hashlib.sha256(table.cpu().numpy().tobytes()).hexdigest()
-    metric(final=1, table_sha256=digest, first_loss=first, loss=last, rank=rank)
+    metric(final=1, table_sha256=digest, first_loss=first, loss=last, rank=rank, **extra)
     log(f"worker {rank}/{nw}: loss {first:.4f} -> {last:.4f}, table {digest[:12]}")
     store.close()
     return 0 if last < first else 1

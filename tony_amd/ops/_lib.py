@@ -235,6 +235,13 @@ _SIGNATURES = {
                           ctypes.POINTER(c_int64), c_int, c_int64, c_void_p],
     "tony_kv_rsp_sgd": [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_int64, c_float, c_float, c_float,
                         c_float, c_int, c_float, c_void_p],
+    # fused optimizer updates of the kvstore (csrc/kv_optim.hip): kind, w, s0, s1, s2, g, n | kind, w, s0, s1, s2,
+    # ids, rows, nnz, row_elems, R; then both: lr, wd, rescale, has_clip, clip, momentum, eps, gamma1, 1 - gamma1,
+    # gamma2, lamda1, beta
+    "tony_kv_opt_dense": [c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_float, c_float,
+                          c_float, c_int] + [c_float] * 8 + [c_void_p],
+    "tony_kv_opt_rows": [c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int64,
+                         c_int64, c_float, c_float, c_float, c_int] + [c_float] * 8 + [c_void_p],
     # Adasum of two flat gradient buffers (csrc/adasum.hip, ops/adasum.py): a, b, is_bf16, items, n_items, partials |
     # partials, order, tstart, T, coef | dst, other, dst_is_a, is_bf16, items, n_items, coef
     "tony_adasum_item_floats": [],

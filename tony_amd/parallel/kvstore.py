@@ -92,6 +92,59 @@ on the plane the worker stores rows, then ids, into its row of the server's wind
 into the worker's landing area, counted on the worker's reply flag; the ordering rules of the dense pull apply
 unchanged.  ``dist_device_sync`` all-gathers ``nnz``, then ids and rows padded to the largest.  A ``RowSparse`` push
 ignores the gradient-compression setting, as MXNet's does.  A store that never sees a ``RowSparse`` runs none of this.
+
+Fused optimizer kinds (``nag``, ``adagrad``, ``rmsprop`` plain and ``centered=True``, ``ftrl``), dense and lazy.  Their
+contract is fixed to the bit as lazy SGD's is: per element, every line below is one separately rounded fp32 operation
+(no contraction); ``sqrt`` and ``/`` are the correctly rounded ones; a constant such as ``1 - gamma1`` is formed in
+double on the host and rounded once to fp32; a NaN stays a NaN (its sign and payload are no part of the contract).
+``g1``, ``g2`` are lazy SGD's (the rescale, then the clip in its comparison form).
+
+``nag`` (state ``mom`` when momentum != 0; at momentum 0 the lines of lazy SGD at momentum 0)::
+
+    p  = wd * w ;  g3 = g2 + p
+    m  = momentum * m ;  m = m + g3
+    q  = momentum * m ;  g4 = g3 + q
+    s  = lr * g4 ;  w = w - s
+
+``adagrad`` (state ``history``; ``epsilon`` 1e-7 by default)::
+
+    q = g2 * g2 ;  h = h + q
+    e = h + eps ;  r = sqrt(e) ;  d = g2 / r
+    p = wd * w ;  u = d + p
+    s = lr * u ;  w = w - s
+
+``rmsprop`` (state ``n``; ``gamma1`` 0.9, ``epsilon`` 1e-8)::
+
+    p = wd * w ;  g3 = g2 + p
+    q = g3 * g3 ;  a = (1-gamma1) * q ;  b = gamma1 * n ;  n = a + b
+    e = n + eps ;  r = sqrt(e) ;  d = g3 / r
+    s = lr * d ;  w = w - s
+
+``rmsprop`` with ``centered=True`` (states ``n``, ``g``, ``delta``; ``gamma2`` 0.9): ``n`` as above, then::
+
+    c  = (1-gamma1) * g3 ;  b2 = gamma1 * gb ;  gb = c + b2
+    gg = gb * gb ;  e1 = n - gg ;  e = e1 + eps
+    r  = sqrt(e) ;  d = g3 / r ;  s = lr * d
+    dl = gamma2 * delta ;  delta = dl - s ;  w = w + delta
+
+``ftrl`` (states ``z``, ``n``; ``lamda1`` 0.01, ``beta`` 1.0; ``wd`` enters only the denominator)::
+
+    q  = g2 * g2 ;  n1 = n + q
+    r1 = sqrt(n1) ;  r0 = sqrt(n) ;  dr = r1 - r0
+    sg = dr / lr ;  t = sg * w
+    z1 = z + g2 ;  z = z1 - t ;  n = n1
+    |z| <= lamda1 :  w = +0.0
+    else:            num = copysign(lamda1, z) - z
+                     b1 = beta + r1 ;  d0 = b1 / lr ;  den = d0 + wd
+                     w = num / den                  # a NaN z fails the comparison: the division carries it on
+
+A contiguous, 16-byte aligned fp32 GPU key with an fp32 gradient runs its update in one launch (``tony_kv_opt_dense``,
+csrc/kv_optim.hip), and the merged push of a row-sparse fp32 GPU key whose rows are a multiple of 16 B in one launch
+on its touched rows (``tony_kv_opt_rows``); CPU tensors, other dtypes (computed in fp32, rounded once on the store)
+and other row lengths run the same lines as separate torch operations, a row-sparse key through the gather / update /
+scatter of lazy Adam.  Lazy updates are lazy SGD's: only the merged rows of the weight and of every state tensor
+(dense ``[R, ...]`` fp32, zero at first use) change.  ``sgd`` and ``adam`` run none of this, and a store that is never
+given one of these kinds runs none of it either.
 """
 from __future__ import annotations
 
@@ -122,19 +175,55 @@ def _dcode(dt: torch.dtype) -> int:
 
 
 # -- optimizers (server- or worker-side updater) -----------------------------------------------
+def _f32(x: float) -> torch.Tensor:
+    """A hyperparameter as the kernels see it: formed in double, rounded once to fp32."""
+    return torch.tensor(float(x), dtype=torch.float32)
+
+
+def _sqrt_rn(x: torch.Tensor) -> torch.Tensor:
+    """The correctly rounded fp32 square root.  On a GPU that is ``torch.sqrt`` (held to the contract bit for bit by
+    tests/test_kv_optim_gpu.py).  ``torch.sqrt`` of a contiguous CPU tensor goes through a vector math
+    library that is off by an ulp now and then; there the root is taken in double and rounded to fp32, which is the
+    correctly rounded one for any faithful double root (scaled to [1, 2), the exact root of an fp32 number is never
+    within 2^-50 of the midpoint of two fp32 numbers -- the square of a midpoint k 2^-24 differs from the number by a
+    multiple of 2^-48 -- and a faithful double root is within 2^-52 of the exact one)."""
+    return torch.sqrt(x) if x.is_cuda else x.double().sqrt().float()
+
+
 class Optimizer:
-    """``mx.optimizer`` subset: sgd (momentum, wd, rescale_grad, clip_gradient) and adam."""
+    """``mx.optimizer`` subset: sgd (momentum, wd, rescale_grad, clip_gradient) and adam, and the kinds whose
+    contract is fixed to the bit (module docstring): nag, adagrad, rmsprop (plain and ``centered``) and ftrl."""
+
+    _FUSED = {"nag": 0, "adagrad": 1, "rmsprop": 2, "ftrl": 4}  # the kinds of csrc/kv_optim.hip (3: centered rmsprop)
+    _EPSILON = {"adagrad": 1e-7}  # the default of a kind when ``epsilon`` is not given (every other kind: 1e-8)
 
     def __init__(self, name: str = "sgd", learning_rate: float = 0.01, momentum: float = 0.0, wd: float = 0.0,
                  rescale_grad: float = 1.0, clip_gradient: Optional[float] = None, beta1: float = 0.9,
-                 beta2: float = 0.999, epsilon: float = 1e-8):
+                 beta2: float = 0.999, epsilon: Optional[float] = None, gamma1: float = 0.9, gamma2: float = 0.9,
+                 centered: bool = False, lamda1: float = 0.01, beta: float = 1.0):
         self.name = name.lower()
-        if self.name not in ("sgd", "adam"):
+        if self.name not in ("sgd", "adam") and self.name not in self._FUSED:
             raise ValueError(f"unsupported optimizer {name!r}")
+        if centered and self.name != "rmsprop":
+            raise ValueError(f"centered=True is an option of rmsprop, not of {self.name!r}")
+        if epsilon is None:
+            epsilon = self._EPSILON.get(self.name, 1e-8)
         self.cfg = dict(name=self.name, learning_rate=learning_rate, momentum=momentum, wd=wd,
                         rescale_grad=rescale_grad, clip_gradient=clip_gradient, beta1=beta1, beta2=beta2,
                         epsilon=epsilon)
+        if self.name in self._FUSED:  # (sgd and adam keep exactly the keys they had)
+            for k, v in (("lamda1", lamda1), ("epsilon", epsilon), ("gamma1", gamma1), ("gamma2", gamma2)):
+                if not float(v) >= 0.0:
+                    raise ValueError(f"{self.name}: {k} must not be negative, not {v!r}")
+            self.cfg.update(gamma1=gamma1, gamma2=gamma2, centered=bool(centered), lamda1=lamda1, beta=beta)
+        else:  # sgd and adam have none of these: a value given to them would be dropped without a word
+            for k, v, default in (("gamma1", gamma1, 0.9), ("gamma2", gamma2, 0.9), ("lamda1", lamda1, 0.01),
+                                  ("beta", beta, 1.0)):
+                if v != default:
+                    raise ValueError(f"{k} is not a hyperparameter of {self.name!r}")
         self.state: Dict[int, dict] = {}
+        self.kernel_ops = [0, 0]  # tony_kv_opt_dense / tony_kv_opt_rows launches (tests)
+        self._scalars: Dict[torch.device, tuple] = {}  # _fused_math's fp32 scalars per device (and the cfg they hold)
 
     def to_json(self) -> str:
         return json.dumps(self.cfg)
@@ -143,7 +232,130 @@ class Optimizer:
     def from_json(cls, s: str) -> "Optimizer":
         return cls(**json.loads(s))
 
+    def _state_names(self) -> tuple:
+        """The names of the state tensors a fused kind's setting keeps per key (``_ROW_STATE``: every one a kind may
+        keep)."""
+        names = self._ROW_STATE[self.name]
+        if self.name == "nag":
+            return names if self.cfg["momentum"] else ()
+        if self.name == "rmsprop" and not self.cfg["centered"]:
+            return names[:1]
+        return names
+
+    def _fused_args(self) -> tuple:
+        """The kind and the hyperparameters of ``tony_kv_opt_dense`` / ``tony_kv_opt_rows`` (csrc/kv_optim.hip)."""
+        c = self.cfg
+        clip = c["clip_gradient"]
+        kind = 3 if c.get("centered") else self._FUSED[self.name]
+        return kind, (c["learning_rate"], c["wd"], c["rescale_grad"], int(clip is not None),
+                      0.0 if clip is None else clip, c["momentum"], c["epsilon"], c["gamma1"], 1 - c["gamma1"],
+                      c["gamma2"], c["lamda1"], c["beta"])
+
+    def _fused_math(self, w: torch.Tensor, st: Dict[str, torch.Tensor], g: torch.Tensor) -> torch.Tensor:
+        """The contract of the module docstring as a torch composition on fp32 tensors of one shape: every op one
+        rounding, every hyperparameter an fp32 scalar.  Returns the new weight; the new states replace ``st``'s."""
+        c = self.cfg
+        # the scalars live on the tensors' device (torch divides by a CPU scalar as a product with its reciprocal) and
+        # are made once per device and setting, not copied there on every update
+        sig, k = self._scalars.get(w.device, (None, None))
+        if sig != tuple(c.values()):
+            k = {n: _f32(v).to(w.device) for n, v in c.items()
+                 if isinstance(v, (int, float)) and not isinstance(v, bool)}
+            k["omg1"] = _f32(1 - c["gamma1"]).to(w.device)
+            self._scalars[w.device] = (tuple(c.values()), k)
+        lr, wd = k["learning_rate"], k["wd"]
+        g2 = g * k["rescale_grad"]
+        if c["clip_gradient"] is not None:
+            cl = k["clip_gradient"]
+            g2 = torch.where(g2 > cl, cl, torch.where(g2 < -cl, -cl, g2))  # a NaN stays NaN
+        if self.name == "nag":
+            g3 = g2 + wd * w
+            if not c["momentum"]:
+                return w - lr * g3
+            mom = k["momentum"]
+            m = mom * st["mom"]
+            m = m + g3
+            st["mom"] = m
+            g4 = g3 + mom * m
+            return w - lr * g4
+        if self.name == "adagrad":
+            h = st["history"] + g2 * g2
+            st["history"] = h
+            r = _sqrt_rn(h + k["epsilon"])
+            u = g2 / r + wd * w
+            return w - lr * u
+        if self.name == "rmsprop":
+            g1, omg, eps = k["gamma1"], k["omg1"], k["epsilon"]
+            g3 = g2 + wd * w
+            a = omg * (g3 * g3)
+            n = a + g1 * st["n"]
+            st["n"] = n
+            if not c["centered"]:
+                return w - lr * (g3 / _sqrt_rn(n + eps))
+            cc = omg * g3
+            gb = cc + g1 * st["g"]
+            st["g"] = gb
+            e = (n - gb * gb) + eps
+            s = lr * (g3 / _sqrt_rn(e))
+            delta = k["gamma2"] * st["delta"] - s
+            st["delta"] = delta
+            return w + delta
+        l1, beta = k["lamda1"], k["beta"]  # ftrl
+        n1 = st["n"] + g2 * g2
+        r1 = _sqrt_rn(n1)
+        sg = (r1 - _sqrt_rn(st["n"])) / lr
+        z = (st["z"] + g2) - sg * w
+        st["z"], st["n"] = z, n1
+        den = (beta + r1) / lr + wd
+        return torch.where(z.abs() <= l1, torch.zeros_like(z), (torch.copysign(l1, z) - z) / den)
+
+    def _update_fused(self, key: int, weight: torch.Tensor, grad: torch.Tensor) -> None:
+        """``update`` of nag / adagrad / rmsprop / ftrl: one ``tony_kv_opt_dense`` launch on a contiguous, 16-byte
+        aligned fp32 GPU key with an fp32 gradient, else the torch composition (other dtypes compute in fp32 and
+        round once on the store)."""
+        if grad.numel() != weight.numel():  # (the kernel would read the gradient's allocation to the key's length)
+            raise ValueError(f"key {key}: a gradient of {grad.numel()} elements for a value of {weight.numel()}")
+        st = self.state.setdefault(key, {"t": 0})
+        names = self._state_names()
+        for n in names:
+            if n not in st:
+                st[n] = torch.zeros(weight.shape, dtype=torch.float32, device=weight.device)
+        if (weight.is_cuda and weight.dtype == torch.float32 and grad.dtype == torch.float32
+                and weight.is_contiguous() and weight.data_ptr() % 16 == 0 and grad.device == weight.device
+                and self._kernel_states(st, names, weight)):
+            from ..ops import _lib
+
+            if not weight.numel():
+                return
+            g = _aligned16(grad)
+            kind, hp = self._fused_args()
+            ptrs = [st[n].data_ptr() for n in names] + [None] * (3 - len(names))
+            with torch.cuda.device(weight.device):
+                _lib.check(_lib.lib().tony_kv_opt_dense(kind, weight.data_ptr(), *ptrs, g.data_ptr(), weight.numel(),
+                                                        *hp, _lib.stream_ptr(weight.device)), "tony_kv_opt_dense")
+            self.kernel_ops[0] += 1
+            return
+        self._update_torch(st, names, weight, grad)
+
+    @staticmethod
+    def _kernel_states(st: dict, names, weight: torch.Tensor) -> bool:
+        """Whether the kernels take the state tensors ``names``: fp32 of the weight's shape on its device, contiguous
+        and 16-byte aligned (a state restored from a file may be anything)."""
+        return all(st[n].device == weight.device and st[n].dtype == torch.float32 and st[n].shape == weight.shape
+                   and st[n].is_contiguous() and st[n].data_ptr() % 16 == 0 for n in names)
+
+    def _update_torch(self, st: dict, names, weight: torch.Tensor, grad: torch.Tensor) -> None:
+        """The fused kinds' update of ``weight`` and the states ``names`` of ``st`` as the torch composition."""
+        new = {n: st[n] for n in names}
+        w = self._fused_math(weight.float(), new, grad.float().reshape(weight.shape))
+        weight.copy_(w)
+        for n in names:
+            st[n].copy_(new[n])
+
     def update(self, key: int, weight: torch.Tensor, grad: torch.Tensor) -> None:
+        if self.name in self._FUSED:
+            self._update_fused(key, weight, grad)
+            return
         c = self.cfg
         g = grad.float() * c["rescale_grad"]
         if c["clip_gradient"] is not None:
@@ -171,12 +383,16 @@ class Optimizer:
         if w is not weight:
             weight.copy_(w)
 
-    _ROW_STATE = {"sgd": ("mom",), "adam": ("m", "v")}
+    _ROW_STATE = {"sgd": ("mom",), "adam": ("m", "v"), "nag": ("mom",), "adagrad": ("history",),
+                  "rmsprop": ("n", "g", "delta"), "ftrl": ("z", "n")}
 
     def _row_state(self, key: int, weight: torch.Tensor):
         """A sparse key's state and the names of its tensors: dense fp32 ``[R, ...]``, zero at first use."""
         st = self.state.setdefault(key, {"t": 0})
-        names = [n for n in self._ROW_STATE[self.name] if self.name == "adam" or self.cfg["momentum"]]
+        if self.name in self._FUSED:
+            names = list(self._state_names())
+        else:
+            names = [n for n in self._ROW_STATE[self.name] if self.name == "adam" or self.cfg["momentum"]]
         for n in names:
             if n not in st:
                 st[n] = torch.zeros(weight.shape, dtype=torch.float32, device=weight.device)
@@ -186,8 +402,10 @@ class Optimizer:
         """The lazy update of a row-sparse key (module docstring): rows ``ids`` (sorted, unique, in range) of the
         dense ``weight`` [R, ...] and of its state from the compact ``grad_rows``; every other row keeps its bits."""
         c = self.cfg
-        st, names = self._row_state(key, weight)
         re = _row_elems(weight.shape)
+        if self.name in self._FUSED and (ids.dim() != 1 or grad_rows.numel() != ids.numel() * re):
+            raise ValueError(f"key {key}: {grad_rows.numel()} gradient elements for {ids.numel()} rows of {re}")
+        st, names = self._row_state(key, weight)
         if (self.name == "sgd" and _rsp_kernel_rows(weight, re) and weight.is_contiguous()
                 and weight.data_ptr() % 16 == 0 and grad_rows.dtype == torch.float32):
             from ..ops import _lib
@@ -202,6 +420,23 @@ class Optimizer:
                     weight.data_ptr(), mom, ids.data_ptr(), g.data_ptr(), ids.numel(), re, weight.shape[0],
                     c["learning_rate"], c["momentum"], c["wd"], c["rescale_grad"], int(clip is not None),
                     0.0 if clip is None else clip, _lib.stream_ptr(weight.device)), "tony_kv_rsp_sgd")
+            return
+        if (self.name in self._FUSED and _rsp_kernel_rows(weight, re) and weight.is_contiguous()
+                and weight.data_ptr() % 16 == 0 and grad_rows.dtype == torch.float32 and ids.dtype == torch.int64
+                and ids.device == weight.device and grad_rows.device == weight.device
+                and self._kernel_states(st, names, weight)):
+            from ..ops import _lib
+
+            if not ids.numel():
+                return
+            ids, g = _aligned16(ids), _aligned16(grad_rows)
+            kind, hp = self._fused_args()
+            ptrs = [st[n].data_ptr() for n in names] + [None] * (3 - len(names))
+            with torch.cuda.device(weight.device):
+                _lib.check(_lib.lib().tony_kv_opt_rows(
+                    kind, weight.data_ptr(), *ptrs, ids.data_ptr(), g.data_ptr(), ids.numel(), re, weight.shape[0],
+                    *hp, _lib.stream_ptr(weight.device)), "tony_kv_opt_rows")
+            self.kernel_ops[1] += 1
             return
         self.update_rows_generic(key, weight, ids, grad_rows)
 
