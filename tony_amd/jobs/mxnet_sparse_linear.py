@@ -5,7 +5,9 @@ The model is one ``[F, D]`` table held by the servers as a sparse key.  A sample
 logit is the sum of their rows projected on a fixed vector.  Every step a worker pulls only the rows its batch
 touches (``row_sparse_pull``), runs forward and backward on them in torch, and pushes only their gradients
 (``RowSparse.from_rows`` sums the rows of a feature that occurs more than once); the servers update only those rows.
-Roles follow DMLC_ROLE as in mxnet_linreg.py.
+``--dot csr`` runs the worker's two halves as ``kv.dot``: the batch is a ``kv.CSR`` (one per batch position, kept
+across epochs, so its transposed plan is made once), the hidden row ``h = kv.dot(x, rows)``, and the pushed gradient
+``kv.dot(x, h.grad, transpose_a=True)``.  Roles follow DMLC_ROLE as in mxnet_linreg.py.
 
   tony --src_dir tony_amd/jobs --executes mxnet_sparse_linear.py --conf tony.application.framework=mxnet \
        --conf tony.scheduler.instances=1 --conf tony.server.instances=1 --conf tony.worker.instances=2 \
@@ -39,6 +41,8 @@ def main(argv=None) -> int:
     ap.add_argument("--optimizer", choices=["sgd", "adam", "adagrad", "ftrl"], default="sgd",
                     help="the servers' (lazy) update of the touched rows")
     ap.add_argument("--device", choices=["auto", "cpu", "cuda"], default="auto")
+    ap.add_argument("--dot", choices=["torch", "csr"], default="torch",
+                    help="the worker's forward and gradient: torch calls, or kv.dot on a kv.CSR of the batch")
     a = ap.parse_args(argv)
     if kv.run_role():  # scheduler / server: serve until the workers are done
         return 0
@@ -57,6 +61,9 @@ def main(argv=None) -> int:
     store.init("table", kv.RowSparse(torch.zeros(0, dtype=torch.int64), torch.zeros(0, D), shape))  # all zero
     store.set_optimizer(kv.create_optimizer(a.optimizer, learning_rate=a.lr, rescale_grad=1.0 / nw))
     extra = {} if a.optimizer == "sgd" else {"optimizer": a.optimizer}  # (the default's output stays as it was)
+    if a.dot == "csr":
+        extra["dot"] = "csr"
+    batches = {}  # --dot csr: the kv.CSR of every batch position
     if extra:
         log(f"worker {rank}/{nw}: optimizer {a.optimizer}, lr {a.lr}")
     rows = kv.RowSparse(torch.zeros(0, dtype=torch.int64, device=dev), torch.zeros(0, D, device=dev), shape)
@@ -68,6 +75,19 @@ def main(argv=None) -> int:
         for lo in range(0, feats.shape[0], a.batch_size):
             fb, yb = feats[lo:lo + a.batch_size], labels[lo:lo + a.batch_size]
             store.row_sparse_pull("table", out=rows, row_ids=fb)
+            if a.dot == "csr":
+                x = batches.get(lo)
+                if x is None:
+                    indptr = torch.arange(fb.shape[0] + 1, device=dev) * a.active
+                    x = batches[lo] = kv.CSR(indptr, fb.reshape(-1), shape=(fb.shape[0], F))
+                h = kv.dot(x, rows).requires_grad_()
+                loss = torch.nn.functional.binary_cross_entropy_with_logits(h @ proj, yb, reduction="sum")
+                loss.backward()
+                store.push("table", kv.dot(x, h.grad, transpose_a=True))
+                total += float(loss)
+                seen += fb.shape[0]
+                rate.add(fb.shape[0])
+                continue
             pos = torch.searchsorted(rows.indices, fb.reshape(-1))         # each occurrence's pulled row
             occ = rows.data.index_select(0, pos).requires_grad_()
             logit = occ.view(fb.shape[0], a.active, D).sum(1) @ proj

@@ -242,6 +242,12 @@ _SIGNATURES = {
                           c_float, c_int] + [c_float] * 8 + [c_void_p],
     "tony_kv_opt_rows": [c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int64,
                          c_int64, c_float, c_float, c_float, c_int] + [c_float] * 8 + [c_void_p],
+    # CSR x row-sparse dot of the kvstore and its transpose (csrc/kv_sparse_dot.hip): out, indptr, indices, data,
+    # w_ids, w_rows, w_n, B, E, row_elems | out, rows, starts, order, src, val, nu, E, nrows, row_elems
+    "tony_kv_csr_dot": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_int64,
+                        c_int64, c_void_p],
+    "tony_kv_rows_segsum": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_int64,
+                            c_int64, c_void_p],
     # Adasum of two flat gradient buffers (csrc/adasum.hip, ops/adasum.py): a, b, is_bf16, items, n_items, partials |
     # partials, order, tstart, T, coef | dst, other, dst_is_a, is_bf16, items, n_items, coef
     "tony_adasum_item_floats": [],

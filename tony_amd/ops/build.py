@@ -43,6 +43,9 @@ HIPCC_FLAGS = [
     "-Wall",
     "-Wno-unused-function",
 ]
+# per translation unit, after HIPCC_FLAGS.  kv_sparse_dot.hip: no packed fp32 operations -- each rn_* call of its
+# bit-fixed contract stays one scalar VALU instruction per element
+EXTRA_FLAGS = {"kv_sparse_dot.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]}
 
 
 def _torch_lib_dir() -> str:
@@ -83,7 +86,7 @@ def build_kernels(verbose: bool = False, force: bool = False) -> str:
         obj = os.path.join(BUILD_DIR, os.path.basename(src) + f".{ARCH}.o")
         objs.append(obj)
         if force or _newer(obj, [src] + headers):
-            cmd = [hipcc, *HIPCC_FLAGS, "-c", src, "-o", obj]
+            cmd = [hipcc, *HIPCC_FLAGS, *EXTRA_FLAGS.get(os.path.basename(src), []), "-c", src, "-o", obj]
             if verbose:
                 print(" ".join(cmd), flush=True)
             procs.append((cmd, subprocess.Popen(cmd, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)))

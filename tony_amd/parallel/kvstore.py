@@ -145,6 +145,31 @@ and other row lengths run the same lines as separate torch operations, a row-spa
 scatter of lazy Adam.  Lazy updates are lazy SGD's: only the merged rows of the weight and of every state tensor
 (dense ``[R, ...]`` fp32, zero at first use) change.  ``sgd`` and ``adam`` run none of this, and a store that is never
 given one of these kinds runs none of it either.
+
+CSR x row-sparse dot (``CSR``, ``dot``): the worker's half of a sparse step, MXNet's ``sparse.dot(csr, weight)`` and
+``sparse.dot(csr, grad, transpose_a=True)``.  ``CSR(indptr, indices, data, shape=(B, F))`` is a batch of ``B`` samples
+over ``F`` columns: int64 ``indptr`` [B + 1], int64 column ids ``indices`` [E], fp32 ``data`` [E] or None (every stored
+value is 1 and no multiply happens); the columns of a sample need not be sorted and may repeat (an embedding bag's
+ids).  The constructor checks ``indptr[0] == 0``, ``indptr`` non-decreasing, ``indptr[-1] == E``, ids in ``[0, F)``,
+``E <= INT32_MAX`` and one device (``ValueError``; one host synchronisation).  Its contract is fixed to the bit, every
+line one separately rounded fp32 operation, no fused multiply-add.  ``dot(x, w)``, ``w`` a ``RowSparse`` or a dense
+tensor of shape ``[F, D]``, returns dense fp32 ``[B, D]``; per sample ``b``, its entries ``e`` in stored order, the ones
+whose column ``c_e`` ``w`` does not hold skipped::
+
+    t_e = data is None ? w_row[c_e] : data[e] * w_row[c_e]
+    acc = t_first ;  acc = acc + t_e   (left to right)          # no such entry: +0.0
+
+``dot(x, dy, transpose_a=True)``, ``dy`` dense ``[B, D]``, returns ``RowSparse(uniq, grad, (F, D))`` -- what ``push``
+takes -- with ``uniq`` the sorted unique columns and ``grad[u]`` the same accumulation over the entries of column
+``uniq[u]`` in ascending entry number with ``t_e = data[e] * dy[rowof[e]]`` (``rowof[e]``: the sample of entry ``e``);
+with ``data`` None this is ``from_rows`` of ``dy`` expanded per occurrence.  The transposed plan (``uniq``, ``starts``
+[nu + 1], ``order``: the entry numbers grouped by column, ascending inside one, and ``rowof``) is made by the stable
+sort ``from_rows`` uses, once per ``CSR``, at the first transposed dot.  fp32 GPU rows of a multiple of 16 B run in one
+launch each (``tony_kv_csr_dot``, ``tony_kv_rows_segsum``, csrc/kv_sparse_dot.hip; tables of at most INT32_MAX rows),
+and so does the tail of ``from_rows`` behind its sort (``tony_kv_rows_segsum`` on the rows as they are); CPU tensors,
+other dtypes (computed in fp32; a gradient rounded once to ``dy``'s dtype) and other row lengths run the same lines as
+torch operations.  ``dot_kernel_ops`` counts the launches of the two entry points.  A process that never builds a
+``CSR`` and never calls ``from_rows`` runs none of this.
 """
 from __future__ import annotations
 
@@ -616,7 +641,14 @@ class RowSparse:
             raise ValueError(f"row ids must be in [0, {shape[0]})")
         sid, order = torch.sort(ids, stable=True)
         uniq, counts = torch.unique_consecutive(sid, return_counts=True)
-        starts = torch.cumsum(counts, 0) - counts
+        ends = torch.cumsum(counts, 0)
+        starts = ends - counts
+        re = _row_elems(shape)
+        if (ids.numel() and _rsp_kernel_rows(rows, re) and ids.device == rows.device
+                and ids.numel() <= _INT32_MAX):  # the sums behind the sort in one launch, nothing read back
+            seg = torch.cat([starts[:1], ends])
+            out = _rows_segsum(rows, seg, order, None, None, ids.numel(), re)
+            return cls(uniq, out.view((uniq.numel(),) + shape[1:]), shape, _checked=True)
         acc = rows.index_select(0, order.index_select(0, starts)).float()
         for k in range(1, int(counts.max()) if ids.numel() else 0):
             sel = (counts > k).nonzero().reshape(-1)
@@ -635,6 +667,167 @@ def _row_elems(shape) -> int:
     for d in shape[1:]:
         n *= int(d)
     return n
+
+
+# -- CSR x row-sparse dot and its transpose (module docstring) -------------------------------------
+_INT32_MAX = 2 ** 31 - 1
+dot_kernel_ops = [0, 0]  # tony_kv_csr_dot / tony_kv_rows_segsum launches (tests)
+
+
+class CSR:
+    """A batch of ``shape[0]`` samples over ``shape[1]`` columns in compressed sparse row form (module docstring):
+    int64 ``indptr`` [B + 1] and ``indices`` [E], fp32 ``data`` [E] or None for all ones."""
+
+    def __init__(self, indptr: torch.Tensor, indices: torch.Tensor, data: Optional[torch.Tensor] = None, shape=None):
+        try:
+            B, F = (int(d) for d in shape)
+        except (TypeError, ValueError):
+            raise ValueError(f"a CSR needs a shape (samples, columns), not {shape!r}") from None
+        if B < 0 or F < 0:
+            raise ValueError(f"a CSR needs a shape (samples, columns), not {shape!r}")
+        for name, t in (("indptr", indptr), ("indices", indices)):
+            if t.dtype != torch.int64 or t.dim() != 1:
+                raise ValueError(f"CSR {name} must be an int64 vector")
+        E = indices.numel()
+        if indptr.numel() != B + 1:
+            raise ValueError(f"CSR indptr of {indptr.numel()} elements for {B} samples")
+        if E > _INT32_MAX:
+            raise ValueError(f"a CSR holds at most {_INT32_MAX} entries, not {E}")
+        if data is not None and (data.dtype != torch.float32 or tuple(data.shape) != (E,)):
+            raise ValueError(f"CSR data must be fp32 of shape ({E},) or None")
+        if indices.device != indptr.device or (data is not None and data.device != indptr.device):
+            raise ValueError("CSR indptr, indices and data must be on the same device")
+        bad = (indptr[0] != 0) | (indptr[-1] != E) | (indptr[1:] < indptr[:-1]).any()
+        if E:
+            bad = bad | (indices.min() < 0) | (indices.max() >= F)
+        if bool(bad):  # (the one host synchronisation of a GPU value)
+            raise ValueError(f"CSR indptr must start at 0, never decrease and end at {E}, the column ids be in "
+                             f"[0, {F})")
+        self.shape = (B, F)
+        self.indptr, self.indices = indptr.contiguous(), indices.contiguous()
+        self.data = None if data is None else data.contiguous()
+        self._plan = self._rowof = None
+
+    @property
+    def nnz(self) -> int:
+        return self.indices.numel()
+
+    def rowof(self) -> torch.Tensor:
+        """The sample of every entry, int64 [E]."""
+        if self._rowof is None:
+            self._rowof = torch.repeat_interleave(torch.arange(self.shape[0], device=self.indices.device),
+                                                  self.indptr[1:] - self.indptr[:-1], output_size=self.nnz)
+        return self._rowof
+
+    def plan(self) -> tuple:
+        """The transposed plan ``(uniq, starts, order, rowof)`` (module docstring), built at the first call."""
+        if self._plan is None:
+            sid, order = torch.sort(self.indices, stable=True)
+            uniq, counts = torch.unique_consecutive(sid, return_counts=True)
+            starts = torch.cat([counts.new_zeros(1), torch.cumsum(counts, 0)])
+            self._plan = (uniq, starts, order, self.rowof())
+        return self._plan
+
+
+def _ordered_segsum_torch(t: torch.Tensor, starts: torch.Tensor) -> torch.Tensor:
+    """Per segment ``[starts[u], starts[u + 1])`` of the fp32 rows ``t`` (no segment empty): ``acc = first; acc = acc
+    + next; ...``, one fp32 add each -- the loop of ``from_rows``."""
+    counts = starts[1:] - starts[:-1]
+    first = starts[:-1]
+    acc = t.index_select(0, first)
+    for k in range(1, int(counts.max()) if counts.numel() else 0):
+        sel = (counts > k).nonzero().reshape(-1)
+        acc.index_copy_(0, sel, acc.index_select(0, sel) + t.index_select(0, first.index_select(0, sel) + k))
+    return acc
+
+
+def _rows_segsum(rows: torch.Tensor, starts: torch.Tensor, order: torch.Tensor, src: Optional[torch.Tensor],
+                 val: Optional[torch.Tensor], E: int, re: int) -> torch.Tensor:
+    """``tony_kv_rows_segsum``: fp32 ``[nu, re]``, row ``u`` the ordered sum over ``k`` in ``[starts[u], starts[u +
+    1])`` of ``val[e] * rows[src[e]]`` (``src`` None: ``rows[e]``; ``val`` None: no multiply), ``e = order[k]``."""
+    from ..ops import _lib
+
+    nu = starts.numel() - 1
+    out = torch.empty((nu, re), dtype=torch.float32, device=rows.device)
+    if not nu:
+        return out
+    rows, starts, order = _aligned16(rows), starts.contiguous(), order.contiguous()
+    src = None if src is None else src.contiguous()
+    val = None if val is None else val.contiguous()
+    with torch.cuda.device(rows.device):
+        _lib.check(_lib.lib().tony_kv_rows_segsum(
+            out.data_ptr(), rows.data_ptr(), starts.data_ptr(), order.data_ptr(), _lib.ptr(src) or None,
+            _lib.ptr(val) or None, nu, E, rows.numel() // re, re, _lib.stream_ptr(rows.device)), "tony_kv_rows_segsum")
+    dot_kernel_ops[1] += 1
+    return out
+
+
+def _dot_forward(x: CSR, w) -> torch.Tensor:
+    B, F = x.shape
+    ids, rows, wshape = (w.indices, w.data, w.shape) if isinstance(w, RowSparse) else (None, w, tuple(w.shape))
+    if len(wshape) != 2 or wshape[0] != F:
+        raise ValueError(f"dot: a CSR of {F} columns times a value of shape {tuple(wshape)}")
+    if rows.device != x.indices.device:
+        raise ValueError("dot: the CSR and w must be on the same device")
+    D, E, n = wshape[1], x.nnz, rows.shape[0]
+    if not (B and E and n):
+        return torch.zeros((B, D), dtype=torch.float32, device=rows.device)
+    if _rsp_kernel_rows(rows, D) and n <= _INT32_MAX:
+        from ..ops import _lib
+
+        rows = _aligned16(rows)
+        ids = None if ids is None else ids.contiguous()
+        out = torch.empty((B, D), dtype=torch.float32, device=rows.device)
+        with torch.cuda.device(rows.device):
+            _lib.check(_lib.lib().tony_kv_csr_dot(
+                out.data_ptr(), x.indptr.data_ptr(), x.indices.data_ptr(), _lib.ptr(x.data) or None,
+                _lib.ptr(ids) or None, rows.data_ptr(), n, B, E, D, _lib.stream_ptr(rows.device)), "tony_kv_csr_dot")
+        dot_kernel_ops[0] += 1
+        return out
+    # the same lines as torch operations: the entries w holds, in stored order, are segments by sample
+    if ids is None:
+        keep, pos = None, x.indices
+    else:
+        pos = torch.searchsorted(ids, x.indices).clamp_(max=n - 1)
+        keep = (ids.index_select(0, pos) == x.indices).nonzero().reshape(-1)
+        pos = pos.index_select(0, keep)
+    t = rows.index_select(0, pos).float()
+    rowof = x.rowof() if keep is None else x.rowof().index_select(0, keep)
+    if x.data is not None:
+        t = t * (x.data if keep is None else x.data.index_select(0, keep)).view(-1, 1)
+    out = torch.zeros((B, D), dtype=torch.float32, device=rows.device)
+    if t.shape[0]:
+        held, counts = torch.unique_consecutive(rowof, return_counts=True)
+        starts = torch.cat([counts.new_zeros(1), torch.cumsum(counts, 0)])
+        out.index_copy_(0, held, _ordered_segsum_torch(t, starts))
+    return out
+
+
+def _dot_transposed(x: CSR, dy: torch.Tensor) -> RowSparse:
+    B, F = x.shape
+    if isinstance(dy, RowSparse) or dy.dim() != 2 or dy.shape[0] != B:
+        raise ValueError(f"dot(transpose_a=True): a CSR of {B} samples times a dense value of {B} rows is wanted")
+    if dy.device != x.indices.device:
+        raise ValueError("dot: the CSR and dy must be on the same device")
+    D, E = dy.shape[1], x.nnz
+    if not E:
+        return RowSparse(torch.zeros(0, dtype=torch.int64, device=dy.device), dy.new_zeros((0, D)), (F, D),
+                         _checked=True)
+    uniq, starts, order, rowof = x.plan()
+    if _rsp_kernel_rows(dy, D) and B <= _INT32_MAX:
+        return RowSparse(uniq, _rows_segsum(dy, starts, order, rowof, x.data, E, D), (F, D), _checked=True)
+    t = dy.float().index_select(0, rowof.index_select(0, order))
+    if x.data is not None:
+        t = t * x.data.index_select(0, order).view(-1, 1)
+    return RowSparse(uniq, _ordered_segsum_torch(t, starts).to(dy.dtype), (F, D), _checked=True)
+
+
+def dot(x: CSR, w, transpose_a: bool = False):
+    """``x @ w`` (dense fp32 ``[B, D]``; ``w`` a ``RowSparse`` or a dense tensor of shape ``[F, D]``) or, with
+    ``transpose_a``, ``x.T @ w`` as a ``RowSparse`` of shape ``(F, D)`` (``w`` dense ``[B, D]``); module docstring."""
+    if not isinstance(x, CSR):
+        raise TypeError("dot takes a CSR as its first operand")
+    return _dot_transposed(x, w) if transpose_a else _dot_forward(x, w)
 
 
 def _unique_row_ids(row_ids: torch.Tensor, rows: int) -> torch.Tensor:
