@@ -36,6 +36,8 @@ def main(argv=None) -> int:
     ap.add_argument("--optimizer", choices=["sgd", "nag", "adam", "adagrad", "rmsprop", "ftrl"], default="sgd")
     ap.add_argument("--gradient-compression", choices=["none", "2bit"], default="none")
     ap.add_argument("--gc-threshold", type=float, default=0.5)
+    ap.add_argument("--key-dtype", choices=["fp32", "bf16", "fp16"], default="fp32")
+    ap.add_argument("--multi-precision", action="store_true")
     a = ap.parse_args(argv)
     if kv.run_role():  # scheduler / server: serve until the workers are done
         return 0
@@ -46,13 +48,19 @@ def main(argv=None) -> int:
     y = 3.0 * x[:, 0] + 0.5 + 0.01 * torch.randn(a.rows, generator=g)
     shard = slice(rank * a.rows // nw, (rank + 1) * a.rows // nw)  # this worker's part of the data
     xs, ys = x[shard], y[shard]
+    kdt = {"fp32": torch.float32, "bf16": torch.bfloat16, "fp16": torch.float16}[a.key_dtype]
     w, b = torch.zeros(1, 1), torch.zeros(1)
-    store.init("fc_weight", w)
-    store.init("fc_bias", b)
-    store.set_optimizer(kv.create_optimizer(a.optimizer, learning_rate=a.lr, rescale_grad=1.0 / (a.batch_size * nw)))
+    store.init("fc_weight", w.to(kdt))
+    store.init("fc_bias", b.to(kdt))
+    mp = {"multi_precision": True} if a.multi_precision else {}  # (the default's setting stays as it was)
+    store.set_optimizer(kv.create_optimizer(a.optimizer, learning_rate=a.lr, rescale_grad=1.0 / (a.batch_size * nw),
+                                            **mp))
     extra = {} if a.optimizer == "sgd" else {"optimizer": a.optimizer}  # (the default's output stays as it was)
     if extra:
         log(f"worker {rank}/{nw}: optimizer {a.optimizer}, lr {a.lr}")
+    if a.key_dtype != "fp32":
+        extra["key_dtype"] = a.key_dtype
+        log(f"worker {rank}/{nw}: {a.key_dtype} keys, multi_precision {a.multi_precision}")
     if a.gradient_compression != "none":  # (the default takes none of the compression code)
         store.set_gradient_compression({"type": a.gradient_compression, "threshold": a.gc_threshold})
     mse = None
@@ -60,10 +68,16 @@ def main(argv=None) -> int:
         for lo in range(0, xs.shape[0], a.batch_size):
             xb, yb = xs[lo:lo + a.batch_size], ys[lo:lo + a.batch_size]
             err = (xb @ w.t())[:, 0] + b - yb                       # forward of FullyConnected(1)
-            store.push("fc_weight", 2 * (err[:, None] * xb).sum(0, keepdim=True))   # d(sum err^2)/dw
-            store.push("fc_bias", 2 * err.sum(0, keepdim=True))
-            store.pull("fc_weight", out=w)
-            store.pull("fc_bias", out=b)
+            store.push("fc_weight", (2 * (err[:, None] * xb).sum(0, keepdim=True)).to(kdt))   # d(sum err^2)/dw
+            store.push("fc_bias", (2 * err.sum(0, keepdim=True)).to(kdt))
+            if kdt == torch.float32:
+                store.pull("fc_weight", out=w)
+                store.pull("fc_bias", out=b)
+            else:  # the stored 16-bit values, widened for the fp32 forward
+                w16, b16 = w.to(kdt), b.to(kdt)
+                store.pull("fc_weight", out=w16)
+                store.pull("fc_bias", out=b16)
+                w, b = w16.float(), b16.float()
         mse = float((((x @ w.t())[:, 0] + b - y) ** 2).mean())
         metric(epoch=epoch, mse=mse, rank=rank, **extra)
     log(f"worker {rank}/{nw}: w={float(w):.3f} b={float(b):.3f} mse={mse:.5f}")

@@ -242,6 +242,14 @@ _SIGNATURES = {
                           c_float, c_int] + [c_float] * 8 + [c_void_p],
     "tony_kv_opt_rows": [c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int64,
                          c_int64, c_float, c_float, c_float, c_int] + [c_float] * 8 + [c_void_p],
+    # multi-precision keys of the kvstore (csrc/kv_mp.hip): kind, is_fp16, w16, w32, s0, s1, s2, then host arrays of
+    # the sources' addresses and dtype codes, nsrc, n | ids, rows, rows' dtype code, nnz, row_elems, R; then both the
+    # hyperparameters of tony_kv_opt_dense
+    "tony_kv_mp_dense": [c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, ctypes.POINTER(c_int64),
+                         ctypes.POINTER(c_int64), c_int, c_int64, c_float, c_float, c_float, c_int] + [c_float] * 8
+                        + [c_void_p],
+    "tony_kv_mp_rows": [c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int,
+                        c_int64, c_int64, c_int64, c_float, c_float, c_float, c_int] + [c_float] * 8 + [c_void_p],
     # CSR x row-sparse dot of the kvstore and its transpose (csrc/kv_sparse_dot.hip): out, indptr, indices, data,
     # w_ids, w_rows, w_n, B, E, row_elems | out, rows, starts, order, src, val, nu, E, nrows, row_elems
     "tony_kv_csr_dot": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_int64,

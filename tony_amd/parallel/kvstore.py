@@ -170,6 +170,39 @@ and so does the tail of ``from_rows`` behind its sort (``tony_kv_rows_segsum`` o
 other dtypes (computed in fp32; a gradient rounded once to ``dy``'s dtype) and other row lengths run the same lines as
 torch operations.  ``dot_kernel_ops`` counts the launches of the two entry points.  A process that never builds a
 ``CSR`` and never calls ``from_rows`` runs none of this.
+
+Multi-precision keys (``create_optimizer(name, ..., multi_precision=True)``, MXNet's ``mp_sgd_update`` and friends).
+The flag is stored in ``cfg`` only when it is true: a setting without it serialises to the JSON it always did.  With
+it, every key whose stored value is ``torch.bfloat16`` or ``torch.float16`` is an mp key, on all four store kinds,
+dense and row-sparse; fp32 keys ignore the flag and 16-bit keys without it behave as they always did.  An mp key's
+optimizer state holds an fp32 master ``w32`` of the key's shape, created at the key's first update as the exact
+widening of the stored value and kept in ``Optimizer.state[key]`` beside the kind's fp32 state tensors (so
+``save_optimizer_states`` / ``load_optimizer_states`` carry it).  An update with sources ``s_0 ... s_{k-1}`` (the
+pushed tensors, each 16-bit or fp32, mixed dtypes allowed) is, per element, every line one separately rounded fp32
+operation::
+
+    g = widen(s_0) ;  g = g + widen(s_i)   (i = 1 ... k-1, in order)      # widening is exact
+    <the kind's lines above, with w := w32 and the gradient := g, states fp32>
+    w32 = new w ;  stored value = rne16(w32)
+
+``rne16`` rounds to nearest even to the key's dtype: for fp16 with subnormals and overflow to +-inf, for both dtypes a
+NaN stays a NaN, and on everything else it gives the bits of ``torch.Tensor.to(dtype)``.  The kinds are lazy SGD's
+lines (both momentum forms, for ``sgd``), ``nag``, ``adagrad``, ``rmsprop`` plain and centered and ``ftrl``; ``adam``
+runs its torch lines on ``w32`` and stores ``rne16(w32)`` (no bit contract, as without the flag).  The sources and
+their order: a local store's pushed list in list order; a ``dist_sync`` round's payloads in worker order, handed to
+the update unsummed instead of being added in the key's dtype first; in ``dist_async`` the one arriving push;
+``dist_device_sync`` keeps its all-reduce in the pushed dtype, whose result is the single source.  A row-sparse mp
+key's pushes go through the ordered merge above (in the pushed dtype) to one merged ``RowSparse``; the lazy update
+then touches only the merged rows of ``w32``, of the states and of the stored 16-bit table, and every other row keeps
+its bits.  Pulls and ``row_sparse_pull`` return the stored 16-bit value.  A contiguous, 16-byte aligned GPU key whose
+sources (at most 8) are contiguous, 16-byte aligned tensors on its device runs its whole round -- the sum, the update
+and the cast -- in one launch (``tony_kv_mp_dense``, csrc/kv_mp.hip; on the GPU plane the sources are the workers' rows
+as the server took them out of its window), and the merged push of a row-sparse one whose rows are a multiple of 16 B
+in the key's dtype in one launch on its touched rows (``tony_kv_mp_rows``); anything else runs the same lines in torch
+on fp32 tensors, bit for bit the same, a row-sparse key through the gather / update / scatter on ``w32``, the states
+and the table.  ``Optimizer.kernel_ops`` of a setting with the flag has two more counters, for these two entry
+points.  A gradient whose element count is not the key's is a ``ValueError`` before any launch.  A store whose
+optimizer lacks the flag runs none of this.
 """
 from __future__ import annotations
 
@@ -225,7 +258,7 @@ class Optimizer:
     def __init__(self, name: str = "sgd", learning_rate: float = 0.01, momentum: float = 0.0, wd: float = 0.0,
                  rescale_grad: float = 1.0, clip_gradient: Optional[float] = None, beta1: float = 0.9,
                  beta2: float = 0.999, epsilon: Optional[float] = None, gamma1: float = 0.9, gamma2: float = 0.9,
-                 centered: bool = False, lamda1: float = 0.01, beta: float = 1.0):
+                 centered: bool = False, lamda1: float = 0.01, beta: float = 1.0, multi_precision: bool = False):
         self.name = name.lower()
         if self.name not in ("sgd", "adam") and self.name not in self._FUSED:
             raise ValueError(f"unsupported optimizer {name!r}")
@@ -248,6 +281,9 @@ class Optimizer:
                     raise ValueError(f"{k} is not a hyperparameter of {self.name!r}")
         self.state: Dict[int, dict] = {}
         self.kernel_ops = [0, 0]  # tony_kv_opt_dense / tony_kv_opt_rows launches (tests)
+        if multi_precision:  # (a setting without it serialises as it always did and counts what it always counted)
+            self.cfg["multi_precision"] = True
+            self.kernel_ops += [0, 0]  # tony_kv_mp_dense / tony_kv_mp_rows launches
         self._scalars: Dict[torch.device, tuple] = {}  # _fused_math's fp32 scalars per device (and the cfg they hold)
 
     def to_json(self) -> str:
@@ -377,7 +413,139 @@ class Optimizer:
         for n in names:
             st[n].copy_(new[n])
 
-    def update(self, key: int, weight: torch.Tensor, grad: torch.Tensor) -> None:
+    _MP_KIND = 6  # lazy SGD among the kinds of csrc/kv_mp.hip (the others: _FUSED's)
+
+    def is_mp(self, weight: torch.Tensor) -> bool:
+        """Whether ``weight`` is the stored value of a multi-precision key under this setting."""
+        return "multi_precision" in self.cfg and weight.dtype in (torch.bfloat16, torch.float16)
+
+    def _mp_names(self) -> tuple:
+        """The fp32 state tensors the kernels of csrc/kv_mp.hip keep beside ``w32`` (adam: none, it runs in torch)."""
+        if self.name in self._FUSED:
+            return self._state_names()
+        return ("mom",) if self.name == "sgd" and self.cfg["momentum"] else ()
+
+    def _mp_state(self, key: int, weight: torch.Tensor, names) -> dict:
+        """An mp key's state: the fp32 master ``w32``, the exact widening of the stored value at the first update, and
+        the fp32 tensors ``names``, zero at first use."""
+        st = self.state.setdefault(key, {"t": 0})
+        if "w32" not in st:
+            st["w32"] = weight.float()
+        for n in names:
+            if n not in st:
+                st[n] = torch.zeros(weight.shape, dtype=torch.float32, device=weight.device)
+        return st
+
+    def _mp_math(self, w: torch.Tensor, st: Dict[str, torch.Tensor], g: torch.Tensor) -> torch.Tensor:
+        """The kind's lines on fp32 tensors as a torch composition, every op one rounding: ``_fused_math``, or lazy
+        SGD's (module docstring).  Returns the new master; the new states replace ``st``'s."""
+        if self.name != "sgd":
+            return self._fused_math(w, st, g)
+        c = self.cfg
+        k = {n: _f32(c[n]).to(w.device) for n in ("learning_rate", "momentum", "wd", "rescale_grad")}
+        g2 = g * k["rescale_grad"]
+        if c["clip_gradient"] is not None:
+            cl = _f32(c["clip_gradient"]).to(w.device)
+            g2 = torch.where(g2 > cl, cl, torch.where(g2 < -cl, -cl, g2))  # a NaN stays NaN
+        s = k["learning_rate"] * (g2 + k["wd"] * w)
+        if not c["momentum"]:
+            return w - s
+        st["mom"] = k["momentum"] * st["mom"] - s
+        return w + st["mom"]
+
+    def _mp_args(self) -> tuple:
+        """The kind and the hyperparameters of ``tony_kv_mp_dense`` / ``tony_kv_mp_rows`` (csrc/kv_mp.hip)."""
+        if self.name in self._FUSED:
+            return self._fused_args()
+        c = self.cfg
+        clip = c["clip_gradient"]
+        return self._MP_KIND, (c["learning_rate"], c["wd"], c["rescale_grad"], int(clip is not None),
+                               0.0 if clip is None else clip, c["momentum"], 0.0, 0.0, 0.0, 0.0, 0.0, 0.0)
+
+    @staticmethod
+    def _mp_source(t: torch.Tensor, device: torch.device) -> bool:
+        """Whether the kernels read the pushed tensor ``t`` in place."""
+        return (t.device == device and t.dtype in (torch.float32, torch.float16, torch.bfloat16)
+                and t.is_contiguous() and t.data_ptr() % 16 == 0)
+
+    def _update_mp(self, key: int, weight: torch.Tensor, srcs: List[torch.Tensor]) -> None:
+        """``update`` of a multi-precision key (module docstring) from its sources, in order: one
+        ``tony_kv_mp_dense`` launch on a contiguous, 16-byte aligned GPU key with at most 8 such sources, else the
+        same lines in torch on fp32 tensors."""
+        for g in srcs:
+            if g.numel() != weight.numel():  # (the kernel would read the source's allocation to the key's length)
+                raise ValueError(f"key {key}: a gradient of {g.numel()} elements for a value of {weight.numel()}")
+        names = self._mp_names()
+        st = self._mp_state(key, weight, names)
+        if (self.name != "adam" and weight.is_cuda and weight.is_contiguous() and weight.data_ptr() % 16 == 0
+                and len(srcs) <= 8 and all(self._mp_source(g, weight.device) for g in srcs)
+                and self._kernel_states(st, names + ("w32",), weight)):
+            import ctypes
+
+            from ..ops import _lib
+
+            if not weight.numel():
+                return
+            kind, hp = self._mp_args()
+            ptrs = [st[n].data_ptr() for n in names] + [None] * (3 - len(names))
+            arr = ctypes.c_int64 * len(srcs)
+            with torch.cuda.device(weight.device):
+                _lib.check(_lib.lib().tony_kv_mp_dense(
+                    kind, int(weight.dtype == torch.float16), weight.data_ptr(), st["w32"].data_ptr(), *ptrs,
+                    arr(*[g.data_ptr() for g in srcs]), arr(*[_dcode(g.dtype) for g in srcs]), len(srcs),
+                    weight.numel(), *hp, _lib.stream_ptr(weight.device)), "tony_kv_mp_dense")
+            self.kernel_ops[2] += 1
+            return
+        self._update_mp_torch(key, weight, st, names, srcs)
+
+    def _update_mp_torch(self, key: int, weight: torch.Tensor, st: dict, names, srcs: List[torch.Tensor]) -> None:
+        """The multi-precision update of ``weight``, ``st["w32"]`` and the states ``names`` as the torch composition."""
+        g = srcs[0].to(weight.device, torch.float32).reshape(weight.shape)
+        for x in srcs[1:]:
+            g = g + x.to(weight.device, torch.float32).reshape(weight.shape)
+        if self.name == "adam":  # its torch lines on the master (no bit contract)
+            self.update(key, st["w32"], g)
+        else:
+            new = {n: st[n] for n in names}
+            st["w32"].copy_(self._mp_math(st["w32"], new, g))
+            for n in names:
+                st[n].copy_(new[n])
+        weight.copy_(st["w32"])  # round to nearest even to the key's dtype
+
+    def _update_rows_mp(self, key: int, weight: torch.Tensor, ids: torch.Tensor, g: torch.Tensor) -> None:
+        """``update_rows`` of a multi-precision key: one ``tony_kv_mp_rows`` launch on the touched rows of the master,
+        the states and the 16-bit table when the rows are a multiple of 16 B in the key's dtype, else the gather /
+        update / scatter on all of them."""
+        re = _row_elems(weight.shape)
+        if ids.dim() != 1 or g.numel() != ids.numel() * re:
+            raise ValueError(f"key {key}: {g.numel()} gradient elements for {ids.numel()} rows of {re}")
+        names = self._mp_names()
+        st = self._mp_state(key, weight, names)
+        if (self.name != "adam" and weight.is_cuda and re > 0 and re % 8 == 0 and weight.is_contiguous()
+                and weight.data_ptr() % 16 == 0 and ids.dtype == torch.int64 and ids.device == weight.device
+                and ids.is_contiguous() and self._mp_source(g, weight.device)
+                and self._kernel_states(st, names + ("w32",), weight)):
+            from ..ops import _lib
+
+            if not ids.numel():
+                return
+            kind, hp = self._mp_args()
+            ptrs = [st[n].data_ptr() for n in names] + [None] * (3 - len(names))
+            with torch.cuda.device(weight.device):
+                _lib.check(_lib.lib().tony_kv_mp_rows(
+                    kind, int(weight.dtype == torch.float16), weight.data_ptr(), st["w32"].data_ptr(), *ptrs,
+                    ids.data_ptr(), g.data_ptr(), _dcode(g.dtype), ids.numel(), re, weight.shape[0], *hp,
+                    _lib.stream_ptr(weight.device)), "tony_kv_mp_rows")
+            self.kernel_ops[3] += 1
+            return
+        self.update_rows_generic(key, weight, ids, g)
+
+    def update(self, key: int, weight: torch.Tensor, grad) -> None:
+        """One update of ``weight`` from ``grad``; a multi-precision key (module docstring) also takes the list of its
+        sources, unsummed."""
+        if self.is_mp(weight):
+            self._update_mp(key, weight, _as_list(grad))
+            return
         if self.name in self._FUSED:
             self._update_fused(key, weight, grad)
             return
@@ -423,9 +591,17 @@ class Optimizer:
                 st[n] = torch.zeros(weight.shape, dtype=torch.float32, device=weight.device)
         return st, names
 
-    def update_rows(self, key: int, weight: torch.Tensor, ids: torch.Tensor, grad_rows: torch.Tensor) -> None:
+    def update_rows(self, key: int, weight: torch.Tensor, ids: torch.Tensor, grad_rows) -> None:
         """The lazy update of a row-sparse key (module docstring): rows ``ids`` (sorted, unique, in range) of the
-        dense ``weight`` [R, ...] and of its state from the compact ``grad_rows``; every other row keeps its bits."""
+        dense ``weight`` [R, ...] and of its state from the compact ``grad_rows``; every other row keeps its bits.
+        A multi-precision key also takes a list of compact gradients of the same ``ids``, summed in fp32 in order."""
+        if self.is_mp(weight):
+            srcs = _as_list(grad_rows)
+            g = srcs[0]
+            for x in srcs[1:]:
+                g = g.float() + x.float()
+            self._update_rows_mp(key, weight, ids, g)
+            return
         c = self.cfg
         re = _row_elems(weight.shape)
         if self.name in self._FUSED and (ids.dim() != 1 or grad_rows.numel() != ids.numel() * re):
@@ -469,6 +645,9 @@ class Optimizer:
         """``update_rows`` for any optimizer, device and dtype: the touched rows of weight and state gathered,
         the dense update's math on them, scattered back."""
         st, names = self._row_state(key, weight)
+        if self.is_mp(weight):  # the master's rows travel with the states'
+            st = self._mp_state(key, weight, ())
+            names = names + ["w32"]
         rows = Optimizer(**self.cfg)
         rows.state[key] = {"t": st["t"], **{n: st[n].index_select(0, ids) for n in names}}
         w = weight.index_select(0, ids)
@@ -973,8 +1152,11 @@ class KVStore:
             if self._sparse_push(kid, _as_list(v)):
                 self._apply_rsp(kid, _rsp_merge(_as_list(v)))
                 continue
-            g = _merge(_as_list(v))
-            self._apply(kid, g)
+            self._apply(kid, _as_list(v) if self._mp_key(kid) else _merge(_as_list(v)))
+
+    def _mp_key(self, kid: int) -> bool:
+        """Whether ``kid`` is a multi-precision key: its pushed list goes to the update unsummed."""
+        return self._opt is not None and kid in self._store and self._opt.is_mp(self._store[kid])
 
     def _apply_rsp(self, kid: int, merged: "RowSparse") -> None:
         if kid not in self._store:
@@ -1008,10 +1190,12 @@ class KVStore:
         src = self._store[kid]
         return _rsp_gather(src, ids.to(src.device))
 
-    def _apply(self, kid: int, merged: torch.Tensor) -> None:
+    def _apply(self, kid: int, merged) -> None:
         if kid not in self._store:
             raise KeyError(f"key {kid} was not initialised")
-        if self._opt is not None:
+        if isinstance(merged, list):  # the sources of a multi-precision key
+            self._opt.update(kid, self._store[kid], [g.to(self._store[kid].device) for g in merged])
+        elif self._opt is not None:
             self._opt.update(kid, self._store[kid], merged.to(self._store[kid].device))
         else:
             self._store[kid].copy_(merged)
@@ -1427,9 +1611,10 @@ class _Server:
             return
         self.sends.append(dist.isend(self.values[kid].contiguous().cpu(), worker, tag=TAG_REPLY))
 
-    def _merge_round(self, kid: int) -> torch.Tensor:
+    def _merge_round(self, kid: int):
         """The open round's pushes of kid summed in worker order (deterministic), on this stream after
-        every plane push's row read (device events: the host never waits for a payload)."""
+        every plane push's row read (device events: the host never waits for a payload).  A multi-precision
+        key's payloads are returned as they are, in worker order: its update sums them."""
         v = self.values[kid]
         merged = None
         if kid in self.rsp:  # row-sparse pushes: the ordered merge of the module docstring
@@ -1439,9 +1624,13 @@ class _Server:
                     torch.cuda.current_stream(v.device).wait_event(ev)
                 vals.append(b)
             return _rsp_merge(vals, v.device)
+        mp = self.opt is not None and self.opt.is_mp(v)
         for _, _, b, ev in sorted(self.round.pop(kid), key=lambda e: (e[0], e[1])):
             if ev is not None:
                 torch.cuda.current_stream(v.device).wait_event(ev)
+            if mp:
+                merged = (merged or []) + [b.to(v.device)]
+                continue
             b = b.to(v.device, v.dtype)  # every payload buffer is this server's own: summed in place
             merged = b if merged is None else merged.add_(b)
         return merged
@@ -1599,8 +1788,9 @@ class _Server:
             s.wait()
 
 
-def run_server(sync: Optional[bool] = None) -> int:
-    """The server role: own keys until every worker sent STOP."""
+def run_server(sync: Optional[bool] = None, stats: Optional[dict] = None) -> int:
+    """The server role: own keys until every worker sent STOP.  ``stats`` (tests), if given, receives the
+    ``kernel_ops`` of the server's optimizer."""
     topo = _Topology()
     store, _ = _init_group(topo)
     dev = None
@@ -1609,7 +1799,10 @@ def run_server(sync: Optional[bool] = None) -> int:
     plane = _make_plane(topo, dev)
     if sync is None:  # every worker announces its kvstore type before its first request
         sync = store.get("tony/kv/type").decode() != "dist_async"
-    _Server(topo, sync, plane).serve()
+    server = _Server(topo, sync, plane)
+    server.serve()
+    if stats is not None and server.opt is not None:
+        stats["kernel_ops"] = list(server.opt.kernel_ops)
     dist.barrier()
     if plane is not None:
         plane.close()
