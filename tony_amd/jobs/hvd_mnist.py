@@ -37,11 +37,15 @@ def main(argv=None) -> int:
     ap.add_argument("--adasum", action="store_true",
                     help="combine the gradients with op=hvd.Adasum instead of averaging them; the learning rate is "
                          "then NOT scaled by size() (needs a power-of-two number of ranks)")
+    ap.add_argument("--fused-stem", action="store_true",
+                    help="run the opening Conv2d(1, 32, 3) + ReLU as one fused op (HIP kernels on GPU ranks)")
     a = ap.parse_args(argv)
     hvd.init()
     dev = hvd.device()
     log(f"hvd rank {hvd.rank()}/{hvd.size()} local {hvd.local_rank()}/{hvd.local_size()} on {dev}")
-    model = mnist_model("hvd_cnn", seed=hvd.rank()).to(dev)
+    model = mnist_model("hvd_cnn", seed=hvd.rank(), fused=a.fused_stem).to(dev)
+    if a.fused_stem:
+        log(f"fused stem: {model[0]}")
     op = hvd.Adasum if a.adasum else hvd.Average
     lr = a.lr if a.adasum else a.lr * hvd.size()
     log(f"gradient reduction op={op} lr={lr:g}")

@@ -37,10 +37,14 @@ def main(argv=None) -> int:
     ap.add_argument("--lr", type=float, default=0.01)
     ap.add_argument("--momentum", type=float, default=0.5)
     ap.add_argument("--checkpoint-steps", type=int, default=0)
+    ap.add_argument("--fused-stem", action="store_true",
+                    help="run a CNN's opening Conv2d(1, 32, k) + ReLU as one fused op (HIP kernels on GPU ranks)")
     a = ap.parse_args(argv)
     rank, world, _, dev = bootstrap.init_from_env()
     log(f"rank {rank}/{world} on {dev}")
-    model = mnist_model(a.model, seed=0).to(dev)
+    model = mnist_model(a.model, seed=0, fused=a.fused_stem).to(dev)
+    if a.fused_stem:
+        log(f"fused stem: {model[0]}")
     ddp = DistributedDataParallel(model)
     opt = torch.optim.SGD(model.parameters(), lr=a.lr, momentum=a.momentum)
     ckpt = CheckpointManager(os.path.join(working_dir(), "mnist_ddp"), save_steps=a.checkpoint_steps, rank=rank)

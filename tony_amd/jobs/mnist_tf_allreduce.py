@@ -30,11 +30,15 @@ def main(argv=None) -> int:
     ap.add_argument("--per-worker-batch", type=int, default=64)
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--lr", type=float, default=0.001)
+    ap.add_argument("--fused-stem", action="store_true",
+                    help="run the opening Conv2d(1, 32, 3) + ReLU as one fused op (HIP kernels on GPU ranks)")
     a = ap.parse_args(argv)
     tc = TFConfig.from_env().without_ps()
     rank, world, dev = bootstrap.init_from_tf_config(tc)
     global_batch = tc.global_batch(a.per_worker_batch)
-    model = mnist_model("keras_cnn", seed=0).to(dev)
+    model = mnist_model("keras_cnn", seed=0, fused=a.fused_stem).to(dev)
+    if a.fused_stem:
+        log(f"fused stem: {model[0]}")
     ddp = DistributedDataParallel(model)
     opt = torch.optim.SGD(model.parameters(), lr=a.lr, momentum=0.5)
     x_all, y_all = synthetic_mnist(global_batch * 4, seed=3, device=dev)

@@ -39,13 +39,17 @@ def main(argv=None) -> int:
     ap.add_argument("--lr", type=float, default=1e-4)
     ap.add_argument("--sync", action="store_true", help="SyncReplicas semantics instead of async")
     ap.add_argument("--model", default="deepnn")
+    ap.add_argument("--fused-stem", action="store_true",
+                    help="run a CNN's opening Conv2d(1, 32, k) + ReLU as one fused op (HIP kernels on GPU ranks)")
     a = ap.parse_args(argv)
     tc = TFConfig.from_env()
     if not tc.ps_ranks:
         log("no ps tasks in the cluster spec")
         return 1
     rank, world, dev = bootstrap.init_from_tf_config(tc)
-    model = mnist_model(a.model, seed=0).to(dev)
+    model = mnist_model(a.model, seed=0, fused=a.fused_stem).to(dev)
+    if a.fused_stem:
+        log(f"fused stem: {model[0]}")
     ps = ParameterServer(model, optimizer="adam", lr=a.lr, mode="dedicated", sync=a.sync, ps_ranks=tc.ps_ranks,
                          dtype=torch.float32, device=dev)
     if ps.is_ps:

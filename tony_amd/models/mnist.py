@@ -48,9 +48,17 @@ def dnn() -> nn.Module:
 MODELS = {"linear": linear, "deepnn": deepnn, "keras_cnn": keras_cnn, "hvd_cnn": hvd_cnn, "dnn": dnn}
 
 
-def mnist_model(name: str = "deepnn", seed: int = 0) -> nn.Module:
+def mnist_model(name: str = "deepnn", seed: int = 0, fused: bool = False) -> nn.Module:
+    """``fused``: the CNNs' opening ``Conv2d(1, 32, k)`` + ReLU as one ``ops.conv1.Conv1BiasReLU`` (HIP on a GPU).  It
+    adopts the parameters of the ``nn.Conv2d`` built here, so the initial bits and the state-dict keys are those of
+    ``fused=False`` (index 1 becomes an ``nn.Identity``); the models without that layer are unchanged."""
     torch.manual_seed(seed)
-    return MODELS[name]()
+    model = MODELS[name]()
+    if fused and name in ("deepnn", "keras_cnn", "hvd_cnn"):
+        from ..ops.conv1 import Conv1BiasReLU
+
+        model[0], model[1] = Conv1BiasReLU(conv=model[0]), nn.Identity()
+    return model
 
 
 def synthetic_mnist(n: int, seed: int = 0, device="cpu"):

@@ -146,6 +146,12 @@ _SIGNATURES = {
     "tony_conv_wgrad_x3": [c_void_p, c_int64, c_void_p, c_int, c_int, c_int, c_int, c_int64, c_int, c_int, c_int,
                            c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p, c_int64, c_void_p, c_int,
                            c_void_p],
+    # single-channel first-layer conv + bias + ReLU of the MNIST CNNs (csrc/conv1.hip, ops/conv1.py): x, w, bias, y, N,
+    # H, W, k, pad | N -> partials | dy, y, x, partials, N, H, W, k, pad | partials, G, k, dw, db
+    "tony_conv1_fwd": [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int, c_int, c_int, c_int, c_void_p],
+    "tony_conv1_bwd_grid": [c_int64],
+    "tony_conv1_bwd": [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int, c_int, c_int, c_int, c_void_p],
+    "tony_conv1_fold": [c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p],
     "tony_x3_wgrad_mode": [c_int],
     "tony_dgrad_one_launch": [c_int],
     "tony_wgrad_pf": [c_int],
