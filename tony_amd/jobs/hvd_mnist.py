@@ -39,13 +39,17 @@ def main(argv=None) -> int:
                          "then NOT scaled by size() (needs a power-of-two number of ranks)")
     ap.add_argument("--fused-stem", action="store_true",
                     help="run the opening Conv2d(1, 32, 3) + ReLU as one fused op (HIP kernels on GPU ranks)")
+    ap.add_argument("--fused-conv2", action="store_true",
+                    help="run Conv2d(32, 64, 3) + ReLU + MaxPool2d(2) as one fused op (HIP kernels on GPU ranks)")
     a = ap.parse_args(argv)
     hvd.init()
     dev = hvd.device()
     log(f"hvd rank {hvd.rank()}/{hvd.size()} local {hvd.local_rank()}/{hvd.local_size()} on {dev}")
-    model = mnist_model("hvd_cnn", seed=hvd.rank(), fused=a.fused_stem).to(dev)
+    model = mnist_model("hvd_cnn", seed=hvd.rank(), fused=a.fused_stem, fused_conv2=a.fused_conv2).to(dev)
     if a.fused_stem:
         log(f"fused stem: {model[0]}")
+    if a.fused_conv2:
+        log(f"fused conv2: {model[2]}")
     op = hvd.Adasum if a.adasum else hvd.Average
     lr = a.lr if a.adasum else a.lr * hvd.size()
     log(f"gradient reduction op={op} lr={lr:g}")

@@ -48,16 +48,27 @@ def dnn() -> nn.Module:
 MODELS = {"linear": linear, "deepnn": deepnn, "keras_cnn": keras_cnn, "hvd_cnn": hvd_cnn, "dnn": dnn}
 
 
-def mnist_model(name: str = "deepnn", seed: int = 0, fused: bool = False) -> nn.Module:
+CONV2_AT = {"deepnn": 3, "hvd_cnn": 2}  # index of the Conv2d(32, 64, k); its ReLU and MaxPool2d(2) follow
+
+
+def mnist_model(name: str = "deepnn", seed: int = 0, fused: bool = False, fused_conv2: bool = False) -> nn.Module:
     """``fused``: the CNNs' opening ``Conv2d(1, 32, k)`` + ReLU as one ``ops.conv1.Conv1BiasReLU`` (HIP on a GPU).  It
     adopts the parameters of the ``nn.Conv2d`` built here, so the initial bits and the state-dict keys are those of
-    ``fused=False`` (index 1 becomes an ``nn.Identity``); the models without that layer are unchanged."""
+    ``fused=False`` (index 1 becomes an ``nn.Identity``); the models without that layer are unchanged.
+
+    ``fused_conv2``: likewise ``deepnn``'s and ``hvd_cnn``'s ``Conv2d(32, 64, k)`` + ReLU + ``MaxPool2d(2)`` as one
+    ``ops.conv2.Conv2BiasReLUPool`` at the convolution's index, an ``nn.Identity`` at the two after it."""
     torch.manual_seed(seed)
     model = MODELS[name]()
     if fused and name in ("deepnn", "keras_cnn", "hvd_cnn"):
         from ..ops.conv1 import Conv1BiasReLU
 
         model[0], model[1] = Conv1BiasReLU(conv=model[0]), nn.Identity()
+    if fused_conv2 and name in CONV2_AT:
+        from ..ops.conv2 import Conv2BiasReLUPool
+
+        i = CONV2_AT[name]
+        model[i], model[i + 1], model[i + 2] = Conv2BiasReLUPool(conv=model[i]), nn.Identity(), nn.Identity()
     return model
 
 

@@ -152,6 +152,15 @@ _SIGNATURES = {
     "tony_conv1_bwd_grid": [c_int64],
     "tony_conv1_bwd": [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int, c_int, c_int, c_int, c_void_p],
     "tony_conv1_fold": [c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p],
+    # 32 -> 64 conv + bias + ReLU + 2x2 max-pool of the MNIST CNNs (csrc/conv2.hip, ops/conv2.py): x, w, bias, y, idx, N,
+    # H, W, k, pad | dy, y, idx, w, dx, ... | N -> slices | dy, y, idx, x, partials, ... | partials, G, k, dw, db
+    "tony_conv2_fwd": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int, c_int, c_int, c_int, c_void_p],
+    "tony_conv2_dgrad": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int, c_int, c_int, c_int,
+                         c_void_p],
+    "tony_conv2_wgrad_grid": [c_int64],
+    "tony_conv2_wgrad": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int, c_int, c_int, c_int,
+                         c_void_p],
+    "tony_conv2_fold": [c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p],
     "tony_x3_wgrad_mode": [c_int],
     "tony_dgrad_one_launch": [c_int],
     "tony_wgrad_pf": [c_int],
