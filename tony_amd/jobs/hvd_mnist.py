@@ -21,7 +21,7 @@ import torch  # noqa: E402
 
 import tony_amd.hvd as hvd  # noqa: E402
 from tony_amd.jobs.common import log, metric, working_dir  # noqa: E402
-from tony_amd.models.mnist import mnist_model, synthetic_mnist  # noqa: E402
+from tony_amd.models.mnist import dense_layers, mnist_model, synthetic_mnist  # noqa: E402
 from tony_amd.utils.checkpoint import CheckpointManager  # noqa: E402
 
 
@@ -41,15 +41,20 @@ def main(argv=None) -> int:
                     help="run the opening Conv2d(1, 32, 3) + ReLU as one fused op (HIP kernels on GPU ranks)")
     ap.add_argument("--fused-conv2", action="store_true",
                     help="run Conv2d(32, 64, 3) + ReLU + MaxPool2d(2) as one fused op (HIP kernels on GPU ranks)")
+    ap.add_argument("--fused-dense", action="store_true",
+                    help="run every nn.Linear, with the ReLU after it, as one fused fp32 op (HIP kernels on GPU ranks)")
     a = ap.parse_args(argv)
     hvd.init()
     dev = hvd.device()
     log(f"hvd rank {hvd.rank()}/{hvd.size()} local {hvd.local_rank()}/{hvd.local_size()} on {dev}")
-    model = mnist_model("hvd_cnn", seed=hvd.rank(), fused=a.fused_stem, fused_conv2=a.fused_conv2).to(dev)
+    model = mnist_model("hvd_cnn", seed=hvd.rank(), fused=a.fused_stem, fused_conv2=a.fused_conv2,
+                        fused_dense=a.fused_dense).to(dev)
     if a.fused_stem:
         log(f"fused stem: {model[0]}")
     if a.fused_conv2:
         log(f"fused conv2: {model[2]}")
+    if a.fused_dense:
+        log(f"fused dense: {[str(model[i]) for i in dense_layers(model)]}")
     op = hvd.Adasum if a.adasum else hvd.Average
     lr = a.lr if a.adasum else a.lr * hvd.size()
     log(f"gradient reduction op={op} lr={lr:g}")

@@ -30,7 +30,7 @@ import torch  # noqa: E402
 import torch.distributed as dist  # noqa: E402
 
 from tony_amd.jobs.common import log, metric, working_dir  # noqa: E402
-from tony_amd.models.mnist import mnist_model, synthetic_mnist  # noqa: E402
+from tony_amd.models.mnist import dense_layers, mnist_model, synthetic_mnist  # noqa: E402
 from tony_amd.parallel import bootstrap  # noqa: E402
 from tony_amd.parallel.flat import FlatParams  # noqa: E402
 from tony_amd.parallel.ps import ParameterServer  # noqa: E402
@@ -76,13 +76,17 @@ def main(argv=None) -> int:
     ap.add_argument("--optimizer", default="adam", choices=["adam", "adagrad"],
                     help="adam (default) or adagrad, the reference job's optimizer (epsilon 1e-5)")
     ap.add_argument("--lr", type=float, default=1e-3, help="learning rate (the reference job's default)")
+    ap.add_argument("--fused-dense", action="store_true",
+                    help="run every nn.Linear, with the ReLU after it, as one fused fp32 op (HIP kernels on GPU ranks)")
     a = ap.parse_args(argv)
     tc = TFConfig.from_env()
     model_dir = working_dir("estimator_model")
     if tc.is_evaluator:
         return evaluate(a, model_dir)
     rank, world, dev = bootstrap.init_from_tf_config(tc)
-    model = mnist_model("dnn", seed=0).to(dev)
+    model = mnist_model("dnn", seed=0, fused_dense=a.fused_dense).to(dev)
+    if a.fused_dense:
+        log(f"fused dense: {[str(model[i]) for i in dense_layers(model)]}")
     opt_kw = {"eps": 1e-5} if a.optimizer == "adagrad" else {}
     ps = ParameterServer(model, optimizer=a.optimizer, lr=a.lr, mode="dedicated", sync=True, ps_ranks=tc.ps_ranks,
                          dtype=torch.float32, device=dev, **opt_kw)

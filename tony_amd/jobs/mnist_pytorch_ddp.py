@@ -22,7 +22,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspa
 import torch  # noqa: E402
 
 from tony_amd.jobs.common import Throughput, log, metric, working_dir  # noqa: E402
-from tony_amd.models.mnist import CONV2_AT, mnist_model, synthetic_mnist  # noqa: E402
+from tony_amd.models.mnist import CONV2_AT, dense_layers, mnist_model, synthetic_mnist  # noqa: E402
 from tony_amd.parallel import bootstrap  # noqa: E402
 from tony_amd.parallel.ddp import DistributedDataParallel  # noqa: E402
 from tony_amd.utils.checkpoint import CheckpointManager, resume_step, training_state  # noqa: E402
@@ -42,14 +42,19 @@ def main(argv=None) -> int:
     ap.add_argument("--fused-conv2", action="store_true",
                     help="run deepnn's / hvd_cnn's Conv2d(32, 64, k) + ReLU + MaxPool2d(2) as one fused op (HIP kernels "
                          "on GPU ranks)")
+    ap.add_argument("--fused-dense", action="store_true",
+                    help="run every nn.Linear, with the ReLU after it, as one fused fp32 op (HIP kernels on GPU ranks)")
     a = ap.parse_args(argv)
     rank, world, _, dev = bootstrap.init_from_env()
     log(f"rank {rank}/{world} on {dev}")
-    model = mnist_model(a.model, seed=0, fused=a.fused_stem, fused_conv2=a.fused_conv2).to(dev)
+    model = mnist_model(a.model, seed=0, fused=a.fused_stem, fused_conv2=a.fused_conv2,
+                        fused_dense=a.fused_dense).to(dev)
     if a.fused_stem:
         log(f"fused stem: {model[0]}")
     if a.fused_conv2 and a.model in CONV2_AT:
         log(f"fused conv2: {model[CONV2_AT[a.model]]}")
+    if a.fused_dense:
+        log(f"fused dense: {[str(model[i]) for i in dense_layers(model)]}")
     ddp = DistributedDataParallel(model)
     opt = torch.optim.SGD(model.parameters(), lr=a.lr, momentum=a.momentum)
     ckpt = CheckpointManager(os.path.join(working_dir(), "mnist_ddp"), save_steps=a.checkpoint_steps, rank=rank)

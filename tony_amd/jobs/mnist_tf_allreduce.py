@@ -19,7 +19,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspa
 import torch  # noqa: E402
 
 from tony_amd.jobs.common import log, metric  # noqa: E402
-from tony_amd.models.mnist import mnist_model, synthetic_mnist  # noqa: E402
+from tony_amd.models.mnist import dense_layers, mnist_model, synthetic_mnist  # noqa: E402
 from tony_amd.parallel import bootstrap  # noqa: E402
 from tony_amd.parallel.ddp import DistributedDataParallel  # noqa: E402
 from tony_amd.parallel.tf_config import TFConfig  # noqa: E402
@@ -32,13 +32,17 @@ def main(argv=None) -> int:
     ap.add_argument("--lr", type=float, default=0.001)
     ap.add_argument("--fused-stem", action="store_true",
                     help="run the opening Conv2d(1, 32, 3) + ReLU as one fused op (HIP kernels on GPU ranks)")
+    ap.add_argument("--fused-dense", action="store_true",
+                    help="run every nn.Linear, with the ReLU after it, as one fused fp32 op (HIP kernels on GPU ranks)")
     a = ap.parse_args(argv)
     tc = TFConfig.from_env().without_ps()
     rank, world, dev = bootstrap.init_from_tf_config(tc)
     global_batch = tc.global_batch(a.per_worker_batch)
-    model = mnist_model("keras_cnn", seed=0, fused=a.fused_stem).to(dev)
+    model = mnist_model("keras_cnn", seed=0, fused=a.fused_stem, fused_dense=a.fused_dense).to(dev)
     if a.fused_stem:
         log(f"fused stem: {model[0]}")
+    if a.fused_dense:
+        log(f"fused dense: {[str(model[i]) for i in dense_layers(model)]}")
     ddp = DistributedDataParallel(model)
     opt = torch.optim.SGD(model.parameters(), lr=a.lr, momentum=0.5)
     x_all, y_all = synthetic_mnist(global_batch * 4, seed=3, device=dev)

@@ -25,7 +25,7 @@ import torch  # noqa: E402
 import torch.distributed as dist  # noqa: E402
 
 from tony_amd.jobs.common import log, metric, working_dir  # noqa: E402
-from tony_amd.models.mnist import CONV2_AT, mnist_model, synthetic_mnist  # noqa: E402
+from tony_amd.models.mnist import CONV2_AT, dense_layers, mnist_model, synthetic_mnist  # noqa: E402
 from tony_amd.parallel import bootstrap  # noqa: E402
 from tony_amd.parallel.ps import ParameterServer  # noqa: E402
 from tony_amd.parallel.tf_config import TFConfig  # noqa: E402
@@ -44,17 +44,22 @@ def main(argv=None) -> int:
     ap.add_argument("--fused-conv2", action="store_true",
                     help="run deepnn's / hvd_cnn's Conv2d(32, 64, k) + ReLU + MaxPool2d(2) as one fused op (HIP kernels "
                          "on GPU ranks)")
+    ap.add_argument("--fused-dense", action="store_true",
+                    help="run every nn.Linear, with the ReLU after it, as one fused fp32 op (HIP kernels on GPU ranks)")
     a = ap.parse_args(argv)
     tc = TFConfig.from_env()
     if not tc.ps_ranks:
         log("no ps tasks in the cluster spec")
         return 1
     rank, world, dev = bootstrap.init_from_tf_config(tc)
-    model = mnist_model(a.model, seed=0, fused=a.fused_stem, fused_conv2=a.fused_conv2).to(dev)
+    model = mnist_model(a.model, seed=0, fused=a.fused_stem, fused_conv2=a.fused_conv2,
+                        fused_dense=a.fused_dense).to(dev)
     if a.fused_stem:
         log(f"fused stem: {model[0]}")
     if a.fused_conv2 and a.model in CONV2_AT:
         log(f"fused conv2: {model[CONV2_AT[a.model]]}")
+    if a.fused_dense:
+        log(f"fused dense: {[str(model[i]) for i in dense_layers(model)]}")
     ps = ParameterServer(model, optimizer="adam", lr=a.lr, mode="dedicated", sync=a.sync, ps_ranks=tc.ps_ranks,
                          dtype=torch.float32, device=dev)
     if ps.is_ps:

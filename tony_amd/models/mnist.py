@@ -7,6 +7,12 @@ keras_cnn    EX/mnist-tensorflow/mnist_keras_distributed.py     Conv2D(32,3) Den
 hvd_cnn      EX/horovod-on-tony/tensorflow2_mnist.py            Conv(32,3) Conv(64,3) pool Dense(128) Dense(10)
                                                                   (1,199,882)
 dnn          EX/mnist-tensorflow/mnist_estimator_distributed.py DNNClassifier([256, 128]) (235,146)
+
+``mnist_model``'s three independent flags move layers onto this project's fp32 HIP kernels without changing a
+state-dict key or an initial bit: ``fused`` (the CNNs' first conv + ReLU, ``ops.conv1``), ``fused_conv2`` (the 32 -> 64
+conv + ReLU + pool, ``ops.conv2``) and ``fused_dense`` (every ``nn.Linear`` with the ``nn.ReLU`` after it,
+``ops.dense``).  With all three, ``hvd_cnn`` and ``keras_cnn`` hold no vendor kernel, as ``dnn`` and ``linear`` do
+with ``fused_dense`` alone; ``deepnn`` keeps its first ``MaxPool2d``.
 """
 from __future__ import annotations
 
@@ -51,13 +57,17 @@ MODELS = {"linear": linear, "deepnn": deepnn, "keras_cnn": keras_cnn, "hvd_cnn":
 CONV2_AT = {"deepnn": 3, "hvd_cnn": 2}  # index of the Conv2d(32, 64, k); its ReLU and MaxPool2d(2) follow
 
 
-def mnist_model(name: str = "deepnn", seed: int = 0, fused: bool = False, fused_conv2: bool = False) -> nn.Module:
+def mnist_model(name: str = "deepnn", seed: int = 0, fused: bool = False, fused_conv2: bool = False,
+                fused_dense: bool = False) -> nn.Module:
     """``fused``: the CNNs' opening ``Conv2d(1, 32, k)`` + ReLU as one ``ops.conv1.Conv1BiasReLU`` (HIP on a GPU).  It
     adopts the parameters of the ``nn.Conv2d`` built here, so the initial bits and the state-dict keys are those of
     ``fused=False`` (index 1 becomes an ``nn.Identity``); the models without that layer are unchanged.
 
     ``fused_conv2``: likewise ``deepnn``'s and ``hvd_cnn``'s ``Conv2d(32, 64, k)`` + ReLU + ``MaxPool2d(2)`` as one
-    ``ops.conv2.Conv2BiasReLUPool`` at the convolution's index, an ``nn.Identity`` at the two after it."""
+    ``ops.conv2.Conv2BiasReLUPool`` at the convolution's index, an ``nn.Identity`` at the two after it.
+
+    ``fused_dense``: every ``nn.Linear`` as an ``ops.dense.Dense`` over that layer's parameters, with ``relu`` set and
+    an ``nn.Identity`` in the ``nn.ReLU``'s place where one follows it.  Independent of the other two flags."""
     torch.manual_seed(seed)
     model = MODELS[name]()
     if fused and name in ("deepnn", "keras_cnn", "hvd_cnn"):
@@ -69,7 +79,22 @@ def mnist_model(name: str = "deepnn", seed: int = 0, fused: bool = False, fused_
 
         i = CONV2_AT[name]
         model[i], model[i + 1], model[i + 2] = Conv2BiasReLUPool(conv=model[i]), nn.Identity(), nn.Identity()
+    if fused_dense:
+        from ..ops.dense import Dense
+
+        for i in dense_layers(model):
+            relu = i + 1 < len(model) and isinstance(model[i + 1], nn.ReLU)
+            model[i] = Dense(linear=model[i], relu=relu)
+            if relu:
+                model[i + 1] = nn.Identity()
     return model
+
+
+def dense_layers(model: nn.Sequential) -> list:
+    """Indices of the model's ``nn.Linear`` layers, or of the ``ops.dense.Dense`` modules ``fused_dense`` put there."""
+    from ..ops.dense import Dense
+
+    return [i for i, m in enumerate(model) if isinstance(m, (nn.Linear, Dense))]
 
 
 def synthetic_mnist(n: int, seed: int = 0, device="cpu"):

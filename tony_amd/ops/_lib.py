@@ -161,6 +161,14 @@ _SIGNATURES = {
     "tony_conv2_wgrad": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int, c_int, c_int, c_int,
                          c_void_p],
     "tony_conv2_fold": [c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p],
+    # fp32 Linear + bias (+ ReLU) of the MNIST dense layers (csrc/dense.hip, ops/dense.py): M, N, K -> K slices S |
+    # x, w, bias, y, partials, M, N, K, relu | partials, bias, y, S, M, N, relu | dy, y, w, dx, M, N, K, relu |
+    # dy, y, x, dw, db, M, N, K, relu
+    "tony_dense_splits": [c_int64, c_int64, c_int64],
+    "tony_dense_fwd": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_int64, c_int, c_void_p],
+    "tony_dense_fold": [c_void_p, c_void_p, c_void_p, c_int, c_int64, c_int64, c_int, c_void_p],
+    "tony_dense_dgrad": [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_int64, c_int, c_void_p],
+    "tony_dense_wgrad": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_int64, c_int, c_void_p],
     "tony_x3_wgrad_mode": [c_int],
     "tony_dgrad_one_launch": [c_int],
     "tony_wgrad_pf": [c_int],
