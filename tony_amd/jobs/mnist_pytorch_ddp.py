@@ -39,6 +39,8 @@ def main(argv=None) -> int:
     ap.add_argument("--checkpoint-steps", type=int, default=0)
     ap.add_argument("--fused-stem", action="store_true",
                     help="run a CNN's opening Conv2d(1, 32, k) + ReLU as one fused op (HIP kernels on GPU ranks)")
+    ap.add_argument("--fused-stem-pool", action="store_true",
+                    help="--fused-stem, with the MaxPool2d(2) that follows the stem in deepnn in the same fused op")
     ap.add_argument("--fused-conv2", action="store_true",
                     help="run deepnn's / hvd_cnn's Conv2d(32, 64, k) + ReLU + MaxPool2d(2) as one fused op (HIP kernels "
                          "on GPU ranks)")
@@ -48,8 +50,8 @@ def main(argv=None) -> int:
     rank, world, _, dev = bootstrap.init_from_env()
     log(f"rank {rank}/{world} on {dev}")
     model = mnist_model(a.model, seed=0, fused=a.fused_stem, fused_conv2=a.fused_conv2,
-                        fused_dense=a.fused_dense).to(dev)
-    if a.fused_stem:
+                        fused_dense=a.fused_dense, fused_pool=a.fused_stem_pool).to(dev)
+    if a.fused_stem or a.fused_stem_pool:
         log(f"fused stem: {model[0]}")
     if a.fused_conv2 and a.model in CONV2_AT:
         log(f"fused conv2: {model[CONV2_AT[a.model]]}")

@@ -8,11 +8,12 @@ hvd_cnn      EX/horovod-on-tony/tensorflow2_mnist.py            Conv(32,3) Conv(
                                                                   (1,199,882)
 dnn          EX/mnist-tensorflow/mnist_estimator_distributed.py DNNClassifier([256, 128]) (235,146)
 
-``mnist_model``'s three independent flags move layers onto this project's fp32 HIP kernels without changing a
-state-dict key or an initial bit: ``fused`` (the CNNs' first conv + ReLU, ``ops.conv1``), ``fused_conv2`` (the 32 -> 64
-conv + ReLU + pool, ``ops.conv2``) and ``fused_dense`` (every ``nn.Linear`` with the ``nn.ReLU`` after it,
-``ops.dense``).  With all three, ``hvd_cnn`` and ``keras_cnn`` hold no vendor kernel, as ``dnn`` and ``linear`` do
-with ``fused_dense`` alone; ``deepnn`` keeps its first ``MaxPool2d``.
+``mnist_model``'s flags move layers onto this project's fp32 HIP kernels without changing a state-dict key or an
+initial bit: ``fused`` (the CNNs' first conv + ReLU, ``ops.conv1``), ``fused_pool`` (``fused`` with the
+``nn.MaxPool2d(2)`` that follows it in ``deepnn`` taken into the same op), ``fused_conv2`` (the 32 -> 64 conv + ReLU +
+pool, ``ops.conv2``) and ``fused_dense`` (every ``nn.Linear`` with the ``nn.ReLU`` after it, ``ops.dense``).  With
+``fused``, ``fused_conv2`` and ``fused_dense``, ``hvd_cnn`` and ``keras_cnn`` hold no vendor kernel, as ``dnn`` and
+``linear`` do with ``fused_dense`` alone; with all four flags ``deepnn`` holds none either.
 """
 from __future__ import annotations
 
@@ -58,7 +59,7 @@ CONV2_AT = {"deepnn": 3, "hvd_cnn": 2}  # index of the Conv2d(32, 64, k); its Re
 
 
 def mnist_model(name: str = "deepnn", seed: int = 0, fused: bool = False, fused_conv2: bool = False,
-                fused_dense: bool = False) -> nn.Module:
+                fused_dense: bool = False, fused_pool: bool = False) -> nn.Module:
     """``fused``: the CNNs' opening ``Conv2d(1, 32, k)`` + ReLU as one ``ops.conv1.Conv1BiasReLU`` (HIP on a GPU).  It
     adopts the parameters of the ``nn.Conv2d`` built here, so the initial bits and the state-dict keys are those of
     ``fused=False`` (index 1 becomes an ``nn.Identity``); the models without that layer are unchanged.
@@ -67,13 +68,20 @@ def mnist_model(name: str = "deepnn", seed: int = 0, fused: bool = False, fused_
     ``ops.conv2.Conv2BiasReLUPool`` at the convolution's index, an ``nn.Identity`` at the two after it.
 
     ``fused_dense``: every ``nn.Linear`` as an ``ops.dense.Dense`` over that layer's parameters, with ``relu`` set and
-    an ``nn.Identity`` in the ``nn.ReLU``'s place where one follows it.  Independent of the other two flags."""
+    an ``nn.Identity`` in the ``nn.ReLU``'s place where one follows it.  Independent of the other two flags.
+
+    ``fused_pool``: implies ``fused``; where an ``nn.MaxPool2d(2)`` follows the first conv's ReLU (``deepnn``) the
+    ``Conv1BiasReLU`` takes it in (``pool=True``) and index 2 becomes an ``nn.Identity`` too.  Independent of
+    ``fused_conv2`` and ``fused_dense``."""
     torch.manual_seed(seed)
     model = MODELS[name]()
-    if fused and name in ("deepnn", "keras_cnn", "hvd_cnn"):
+    if (fused or fused_pool) and name in ("deepnn", "keras_cnn", "hvd_cnn"):
         from ..ops.conv1 import Conv1BiasReLU
 
-        model[0], model[1] = Conv1BiasReLU(conv=model[0]), nn.Identity()
+        pool = fused_pool and isinstance(model[2], nn.MaxPool2d) and model[2].kernel_size == 2
+        model[0], model[1] = Conv1BiasReLU(conv=model[0], pool=pool), nn.Identity()
+        if pool:
+            model[2] = nn.Identity()
     if fused_conv2 and name in CONV2_AT:
         from ..ops.conv2 import Conv2BiasReLUPool
 

@@ -152,6 +152,13 @@ _SIGNATURES = {
     "tony_conv1_bwd_grid": [c_int64],
     "tony_conv1_bwd": [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int, c_int, c_int, c_int, c_void_p],
     "tony_conv1_fold": [c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p],
+    # the same layer with deepnn's 2x2 max-pool (csrc/conv1_pool.hip, ops/conv1.py pool=True): x, w, bias, y, idx, N, H,
+    # W, k, pad | N -> partials | dy, y, idx, x, partials, N, H, W, k, pad; the partials go through tony_conv1_fold
+    "tony_conv1_pool_fwd": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int, c_int, c_int, c_int,
+                            c_void_p],
+    "tony_conv1_pool_bwd_grid": [c_int64],
+    "tony_conv1_pool_bwd": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int, c_int, c_int, c_int,
+                            c_void_p],
     # 32 -> 64 conv + bias + ReLU + 2x2 max-pool of the MNIST CNNs (csrc/conv2.hip, ops/conv2.py): x, w, bias, y, idx, N,
     # H, W, k, pad | dy, y, idx, w, dx, ... | N -> slices | dy, y, idx, x, partials, ... | partials, G, k, dw, db
     "tony_conv2_fwd": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int, c_int, c_int, c_int, c_void_p],

@@ -1,4 +1,5 @@
-"""Single-channel first-layer conv + bias + ReLU of the MNIST CNNs (HIP kernels in csrc/conv1.hip).
+"""Single-channel first-layer conv + bias + ReLU (+ 2x2 max-pool) of the MNIST CNNs (HIP kernels in csrc/conv1.hip and
+csrc/conv1_pool.hip).
 
 ``conv1_bias_relu(x, weight, bias, padding)`` is ``relu(conv2d(x, weight, bias, padding=padding))`` for the layer
 ``deepnn``, ``keras_cnn`` and ``hvd_cnn`` open with.  The kernels take this form::
@@ -14,6 +15,13 @@ On a GPU a tensor of the form above never takes that path: a missing kernel libr
 Forward is one launch (``tony_conv1_fwd``); backward is two (``tony_conv1_bwd`` stores one 32x32 partial of
 ``[dW | db]`` per workgroup, ``tony_conv1_fold`` adds them in index order).  The gradient at ``y == 0`` is 0, torch's
 convention.  No atomics: the same inputs give the same bits.
+
+``pool=True`` is ``max_pool2d(relu(conv2d(...)), 2)``, ``deepnn``'s opening: the same form with ``OH, OW >= 2``, and
+anything else is exactly that torch composition.  Forward is one launch (``tony_conv1_pool_fwd``) that writes the
+pooled ``y`` and a uint8 ``idx``, the window position 0..3 of each maximum (the first one in row-major order, torch's
+rule); an odd ``OH`` or ``OW`` is pooled with floor and the last conv row or column is never computed.  Backward is
+``tony_conv1_pool_bwd`` over ``(dy, y, idx, x)`` and the same ``tony_conv1_fold``.  Neither the full-resolution
+activation nor its gradient is ever written.  With ``pool=False`` nothing differs from what is described above.
 """
 from __future__ import annotations
 
@@ -74,19 +82,73 @@ class _Conv1BiasReLU(torch.autograd.Function):
         return None, dw, db, None
 
 
-def conv1_bias_relu(x, weight, bias, padding: int = 0):
-    """``relu(conv2d(x, weight, bias, padding=padding))``: the HIP kernels for the form in the module docstring, the
-    torch composition itself for everything else."""
+def _native_pool(x, weight, bias, padding) -> bool:
+    if not _native(x, weight, bias, padding):
+        return False
+    k = weight.shape[-1]
+    return x.shape[2] + 2 * padding - k + 1 >= 2 and x.shape[3] + 2 * padding - k + 1 >= 2
+
+
+def _forward_pool(x, weight, bias, padding):
+    """The pooled ``y`` and its ``idx`` from ``tony_conv1_pool_fwd`` (``x`` of the native form)."""
+    n, _, h, w = x.shape
+    k = weight.shape[-1]
+    shape = (n, COUT, (h + 2 * padding - k + 1) // 2, (w + 2 * padding - k + 1) // 2)
+    y = torch.empty(shape, dtype=torch.float32, device=x.device)
+    idx = torch.empty(shape, dtype=torch.uint8, device=x.device)
+    with torch.cuda.device(x.device):
+        rc = _lib.lib().tony_conv1_pool_fwd(x.data_ptr(), weight.data_ptr(), bias.data_ptr(), y.data_ptr(),
+                                            idx.data_ptr(), n, h, w, k, padding, _lib.stream_ptr(x.device))
+    _lib.check(rc, "tony_conv1_pool_fwd")
+    return y, idx
+
+
+class _Conv1BiasReLUPool(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, weight, bias, padding):
+        y, idx = _forward_pool(x, weight, bias, padding)
+        ctx.save_for_backward(x, y, idx)
+        ctx.geom = (weight.shape[-1], padding)
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        x, y, idx = ctx.saved_tensors
+        k, padding = ctx.geom
+        n, _, h, w = x.shape
+        dy = dy.contiguous()
+        L = _lib.lib()
+        grid = L.tony_conv1_pool_bwd_grid(n)
+        partials = torch.empty(grid * COUT * 32, dtype=torch.float32, device=x.device)
+        dw = torch.empty(COUT, 1, k, k, dtype=torch.float32, device=x.device)
+        db = torch.empty(COUT, dtype=torch.float32, device=x.device)
+        with torch.cuda.device(x.device):
+            stream = _lib.stream_ptr(x.device)
+            _lib.check(L.tony_conv1_pool_bwd(dy.data_ptr(), y.data_ptr(), idx.data_ptr(), x.data_ptr(),
+                                             partials.data_ptr(), n, h, w, k, padding, stream), "tony_conv1_pool_bwd")
+            _lib.check(L.tony_conv1_fold(partials.data_ptr(), grid, k, dw.data_ptr(), db.data_ptr(), stream),
+                       "tony_conv1_fold")
+        return None, dw, db, None
+
+
+def conv1_bias_relu(x, weight, bias, padding: int = 0, pool: bool = False):
+    """``relu(conv2d(x, weight, bias, padding=padding))``, under ``max_pool2d(., 2)`` with ``pool``: the HIP kernels for
+    the form in the module docstring, the torch composition itself for everything else."""
+    if pool:
+        if _native_pool(x, weight, bias, padding):
+            return _Conv1BiasReLUPool.apply(x, weight, bias, padding)
+        return F.max_pool2d(F.relu(F.conv2d(x, weight, bias, padding=padding)), 2)
     if _native(x, weight, bias, padding):
         return _Conv1BiasReLU.apply(x, weight, bias, padding)
     return F.relu(F.conv2d(x, weight, bias, padding=padding))
 
 
 class Conv1BiasReLU(nn.Module):
-    """``nn.Conv2d(1, 32, kernel_size, padding=padding)`` followed by ReLU as one op; ``weight`` and ``bias`` have
-    ``nn.Conv2d``'s names, shapes and initial values (they ARE those of an ``nn.Conv2d`` built here, or of ``conv``)."""
+    """``nn.Conv2d(1, 32, kernel_size, padding=padding)`` followed by ReLU (and by ``nn.MaxPool2d(2)`` with ``pool``) as
+    one op; ``weight`` and ``bias`` have ``nn.Conv2d``'s names, shapes and initial values (they ARE those of an
+    ``nn.Conv2d`` built here, or of ``conv``)."""
 
-    def __init__(self, kernel_size: int = 3, padding: int = 0, conv: nn.Conv2d = None):
+    def __init__(self, kernel_size: int = 3, padding: int = 0, conv: nn.Conv2d = None, pool: bool = False):
         super().__init__()
         if conv is None:
             conv = nn.Conv2d(1, COUT, kernel_size, padding=padding)
@@ -94,11 +156,12 @@ class Conv1BiasReLU(nn.Module):
                 or conv.bias is None or conv.kernel_size[0] != conv.kernel_size[1] or conv.padding[0] != conv.padding[1] \
                 or not isinstance(conv.padding[0], int) or conv.padding_mode != "zeros":
             raise ValueError(f"Conv1BiasReLU replaces Conv2d(1, {COUT}, k, padding=p) with a bias, got {conv}")
-        self.kernel_size, self.padding = conv.kernel_size[0], conv.padding[0]
+        self.kernel_size, self.padding, self.pool = conv.kernel_size[0], conv.padding[0], pool
         self.weight, self.bias = conv.weight, conv.bias
 
     def forward(self, x):
-        return conv1_bias_relu(x, self.weight, self.bias, self.padding)
+        return conv1_bias_relu(x, self.weight, self.bias, self.padding, self.pool)
 
     def extra_repr(self) -> str:
-        return f"1, {COUT}, kernel_size={self.kernel_size}, padding={self.padding}"
+        s = f"1, {COUT}, kernel_size={self.kernel_size}, padding={self.padding}"
+        return s + ", pool=True" if self.pool else s

@@ -10,6 +10,8 @@ per-worker batch, and 128.  Forward: ``tony_conv1_fwd`` against ``F.relu(F.conv2
 backward of either graph (``x`` not requiring grad), which for the kernels is ``tony_conv1_bwd`` + ``tony_conv1_fold``.
 Bytes: the forward reads x and writes y, the backward reads dy, y and x; a ``tony_kv_copy`` moves each count, half read
 and half written.  These tensors fit in the caches, so the copy is a latency yardstick more than a bandwidth one.
+After them the deepnn form with its 2x2 max-pool at both batches ("pooled"): ``conv1_bias_relu(..., pool=True)``, i.e.
+``tony_conv1_pool_fwd`` and ``tony_conv1_pool_bwd`` + ``tony_conv1_fold``, against ``F.max_pool2d`` over the composition.
 Prints per arm the median / min / max us per launch over the rounds, then whether each kernel arm's slowest round is
 below the composition's fastest.
 """
@@ -32,7 +34,7 @@ def main():
     ap.add_argument("--rounds", type=int, default=5)
     a = ap.parse_args()
     from tony_amd.ops import _lib
-    from tony_amd.ops.conv1 import _Conv1BiasReLU, conv1_bias_relu
+    from tony_amd.ops.conv1 import _Conv1BiasReLU, _Conv1BiasReLUPool, conv1_bias_relu
 
     L = _lib.lib()
     dev = torch.device("cuda", 0)
@@ -61,6 +63,25 @@ def main():
                      (case, "bwd kernel", lambda y=y_k, w=w, b=b, dy=dy: torch.autograd.grad(y, (w, b), dy, retain_graph=True)),
                      (case, "bwd torch", lambda y=y_t, w=w, b=b, dy=dy: torch.autograd.grad(y, (w, b), dy, retain_graph=True)),
                      (case, f"bwd copy {bwd_bytes / 1e6:.1f} MB", copy(bwd_bytes))]
+    # deepnn's form with its 2x2 max-pool in the op (csrc/conv1_pool.hip): pooled y and a uint8 idx instead of the
+    # full-resolution y, against max_pool2d over the composition
+    label, k, p = FORMS[1]
+    for n in (64, 128):
+        case = f"{label} pooled batch {n}"
+        x = torch.rand(n, 1, 28, 28, device=dev, generator=gen)
+        w = (torch.randn(32, 1, k, k, device=dev, generator=gen) * 0.2).requires_grad_()
+        b = torch.zeros(32, device=dev).requires_grad_()
+        y_k = conv1_bias_relu(x, w, b, p, pool=True)
+        y_t = F.max_pool2d(F.relu(F.conv2d(x, w, b, padding=p)), 2)
+        assert isinstance(y_k.grad_fn, _Conv1BiasReLUPool._backward_cls) and y_k.shape == y_t.shape
+        dy = torch.randn(y_k.shape, device=dev, generator=gen)
+        fwd_bytes, bwd_bytes = 4 * x.numel() + 5 * y_k.numel(), 4 * x.numel() + 9 * y_k.numel()
+        arms += [(case, "fwd kernel", lambda x=x, w=w, b=b, p=p: conv1_bias_relu(x, w, b, p, pool=True)),
+                 (case, "fwd torch", lambda x=x, w=w, b=b, p=p: F.max_pool2d(F.relu(F.conv2d(x, w, b, padding=p)), 2)),
+                 (case, f"fwd copy {fwd_bytes / 1e6:.1f} MB", copy(fwd_bytes)),
+                 (case, "bwd kernel", lambda y=y_k, w=w, b=b, dy=dy: torch.autograd.grad(y, (w, b), dy, retain_graph=True)),
+                 (case, "bwd torch", lambda y=y_t, w=w, b=b, dy=dy: torch.autograd.grad(y, (w, b), dy, retain_graph=True)),
+                 (case, f"bwd copy {bwd_bytes / 1e6:.1f} MB", copy(bwd_bytes))]
     for _, _, fn in arms:  # warm up: code objects loaded, MIOpen's algorithms chosen, clocks up
         for _ in range(10):
             fn()
