@@ -21,7 +21,7 @@ import torch  # noqa: E402
 
 import tony_amd.hvd as hvd  # noqa: E402
 from tony_amd.jobs.common import log, metric, working_dir  # noqa: E402
-from tony_amd.models.mnist import dense_layers, mnist_model, synthetic_mnist  # noqa: E402
+from tony_amd.models.mnist import dense_layers, mnist_loss, mnist_model, synthetic_mnist  # noqa: E402
 from tony_amd.utils.checkpoint import CheckpointManager  # noqa: E402
 
 
@@ -43,6 +43,9 @@ def main(argv=None) -> int:
                     help="run Conv2d(32, 64, 3) + ReLU + MaxPool2d(2) as one fused op (HIP kernels on GPU ranks)")
     ap.add_argument("--fused-dense", action="store_true",
                     help="run every nn.Linear, with the ReLU after it, as one fused fp32 op (HIP kernels on GPU ranks)")
+    ap.add_argument("--fused-head", action="store_true",
+                    help="run the last nn.Linear and the cross-entropy after it as one fused op (HIP kernels on GPU "
+                         "ranks)")
     a = ap.parse_args(argv)
     hvd.init()
     dev = hvd.device()
@@ -55,6 +58,8 @@ def main(argv=None) -> int:
         log(f"fused conv2: {model[2]}")
     if a.fused_dense:
         log(f"fused dense: {[str(model[i]) for i in dense_layers(model)]}")
+    if a.fused_head:
+        log(f"fused head: {model[-1]} + cross-entropy")
     op = hvd.Adasum if a.adasum else hvd.Average
     lr = a.lr if a.adasum else a.lr * hvd.size()
     log(f"gradient reduction op={op} lr={lr:g}")
@@ -69,7 +74,7 @@ def main(argv=None) -> int:
     for s in range(a.steps):
         lo = ((s % 4) * hvd.size() + hvd.rank()) * a.batch_size
         opt.zero_grad()
-        loss = torch.nn.functional.cross_entropy(model(x_all[lo:lo + a.batch_size]), y_all[lo:lo + a.batch_size])
+        loss = mnist_loss(model, x_all[lo:lo + a.batch_size], y_all[lo:lo + a.batch_size], a.fused_head)
         loss.backward()
         opt.step()
         losses.append(float(loss))

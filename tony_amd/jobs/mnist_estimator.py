@@ -30,7 +30,7 @@ import torch  # noqa: E402
 import torch.distributed as dist  # noqa: E402
 
 from tony_amd.jobs.common import log, metric, working_dir  # noqa: E402
-from tony_amd.models.mnist import dense_layers, mnist_model, synthetic_mnist  # noqa: E402
+from tony_amd.models.mnist import dense_layers, mnist_loss, mnist_model, synthetic_mnist  # noqa: E402
 from tony_amd.parallel import bootstrap  # noqa: E402
 from tony_amd.parallel.flat import FlatParams  # noqa: E402
 from tony_amd.parallel.ps import ParameterServer  # noqa: E402
@@ -78,6 +78,9 @@ def main(argv=None) -> int:
     ap.add_argument("--lr", type=float, default=1e-3, help="learning rate (the reference job's default)")
     ap.add_argument("--fused-dense", action="store_true",
                     help="run every nn.Linear, with the ReLU after it, as one fused fp32 op (HIP kernels on GPU ranks)")
+    ap.add_argument("--fused-head", action="store_true",
+                    help="run the last nn.Linear and the cross-entropy after it as one fused op (HIP kernels on GPU "
+                         "ranks)")
     a = ap.parse_args(argv)
     tc = TFConfig.from_env()
     model_dir = working_dir("estimator_model")
@@ -87,6 +90,8 @@ def main(argv=None) -> int:
     model = mnist_model("dnn", seed=0, fused_dense=a.fused_dense).to(dev)
     if a.fused_dense:
         log(f"fused dense: {[str(model[i]) for i in dense_layers(model)]}")
+    if a.fused_head:
+        log(f"fused head: {model[-1]} + cross-entropy")
     opt_kw = {"eps": 1e-5} if a.optimizer == "adagrad" else {}
     ps = ParameterServer(model, optimizer=a.optimizer, lr=a.lr, mode="dedicated", sync=True, ps_ranks=tc.ps_ranks,
                          dtype=torch.float32, device=dev, **opt_kw)
@@ -99,7 +104,7 @@ def main(argv=None) -> int:
         if ps.is_worker:
             lo = (((s - 1) % 4) * len(ps.worker_ranks) + widx) * a.batch_size
             ps.zero_grad()
-            loss = torch.nn.functional.cross_entropy(model(x_all[lo:lo + a.batch_size]), y_all[lo:lo + a.batch_size])
+            loss = mnist_loss(model, x_all[lo:lo + a.batch_size], y_all[lo:lo + a.batch_size], a.fused_head)
             loss.backward()
             if tc.is_chief and (s == 1 or s % max(1, a.save_steps) == 0 or s == a.steps):
                 log(f"step {s}: loss {float(loss):.4f} ({a.optimizer})")

@@ -25,7 +25,7 @@ import torch  # noqa: E402
 import torch.distributed as dist  # noqa: E402
 
 from tony_amd.jobs.common import log, metric, working_dir  # noqa: E402
-from tony_amd.models.mnist import CONV2_AT, dense_layers, mnist_model, synthetic_mnist  # noqa: E402
+from tony_amd.models.mnist import CONV2_AT, dense_layers, mnist_loss, mnist_model, synthetic_mnist  # noqa: E402
 from tony_amd.parallel import bootstrap  # noqa: E402
 from tony_amd.parallel.ps import ParameterServer  # noqa: E402
 from tony_amd.parallel.tf_config import TFConfig  # noqa: E402
@@ -48,6 +48,9 @@ def main(argv=None) -> int:
                          "on GPU ranks)")
     ap.add_argument("--fused-dense", action="store_true",
                     help="run every nn.Linear, with the ReLU after it, as one fused fp32 op (HIP kernels on GPU ranks)")
+    ap.add_argument("--fused-head", action="store_true",
+                    help="run the last nn.Linear and the cross-entropy after it as one fused op (HIP kernels on GPU "
+                         "ranks)")
     a = ap.parse_args(argv)
     tc = TFConfig.from_env()
     if not tc.ps_ranks:
@@ -62,6 +65,8 @@ def main(argv=None) -> int:
         log(f"fused conv2: {model[CONV2_AT[a.model]]}")
     if a.fused_dense:
         log(f"fused dense: {[str(model[i]) for i in dense_layers(model)]}")
+    if a.fused_head:
+        log(f"fused head: {model[-1]} + cross-entropy")
     ps = ParameterServer(model, optimizer="adam", lr=a.lr, mode="dedicated", sync=a.sync, ps_ranks=tc.ps_ranks,
                          dtype=torch.float32, device=dev)
     if ps.is_ps:
@@ -82,7 +87,7 @@ def main(argv=None) -> int:
     for s in range(a.steps):
         lo = ((s % 4) * len(ps.worker_ranks) + widx) * a.batch_size
         ps.zero_grad()
-        loss = torch.nn.functional.cross_entropy(model(x_all[lo:lo + a.batch_size]), y_all[lo:lo + a.batch_size])
+        loss = mnist_loss(model, x_all[lo:lo + a.batch_size], y_all[lo:lo + a.batch_size], a.fused_head)
         loss.backward()
         ps.step()
         losses.append(float(loss))

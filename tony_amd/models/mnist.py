@@ -13,7 +13,8 @@ initial bit: ``fused`` (the CNNs' first conv + ReLU, ``ops.conv1``), ``fused_poo
 ``nn.MaxPool2d(2)`` that follows it in ``deepnn`` taken into the same op), ``fused_conv2`` (the 32 -> 64 conv + ReLU +
 pool, ``ops.conv2``) and ``fused_dense`` (every ``nn.Linear`` with the ``nn.ReLU`` after it, ``ops.dense``).  With
 ``fused``, ``fused_conv2`` and ``fused_dense``, ``hvd_cnn`` and ``keras_cnn`` hold no vendor kernel, as ``dnn`` and
-``linear`` do with ``fused_dense`` alone; with all four flags ``deepnn`` holds none either.
+``linear`` do with ``fused_dense`` alone; with all four flags ``deepnn`` holds none either.  ``mnist_loss`` is the jobs'
+loss line; its ``fused_head`` takes the last layer and the cross-entropy after it into one op (``ops.dense_xent``).
 """
 from __future__ import annotations
 
@@ -103,6 +104,24 @@ def dense_layers(model: nn.Sequential) -> list:
     from ..ops.dense import Dense
 
     return [i for i, m in enumerate(model) if isinstance(m, (nn.Linear, Dense))]
+
+
+def mnist_loss(model: nn.Sequential, x, y, fused_head: bool = False):
+    """The jobs' training loss, ``F.cross_entropy(model(x), y)``.  ``fused_head``: the layers before the last one run
+    as they are and the closing ``Linear(K, 10)`` and the loss become one ``ops.dense_xent.dense_xent`` over that
+    layer's ``weight`` and ``bias`` (one HIP launch each way on a GPU).  No module is replaced, so the state-dict keys
+    and the initial bits are those of the model as built."""
+    if not fused_head:
+        return torch.nn.functional.cross_entropy(model(x), y)
+    from ..ops.dense import Dense
+    from ..ops.dense_xent import dense_xent
+
+    *body, head = model  # what model[:-1](x) runs, without building that nn.Sequential every step
+    if not (isinstance(head, nn.Linear) or (isinstance(head, Dense) and not head.relu)) or head.bias is None:
+        raise TypeError(f"fused_head takes a model that ends in a Linear with a bias and no ReLU, got {head}")
+    for layer in body:
+        x = layer(x)
+    return dense_xent(x, head.weight, head.bias, y)
 
 
 def synthetic_mnist(n: int, seed: int = 0, device="cpu"):

@@ -176,6 +176,12 @@ _SIGNATURES = {
     "tony_dense_fold": [c_void_p, c_void_p, c_void_p, c_int, c_int64, c_int64, c_int, c_void_p],
     "tony_dense_dgrad": [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_int64, c_int, c_void_p],
     "tony_dense_wgrad": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_int64, c_int, c_void_p],
+    # the classifier head Linear(K, N <= 32) + softmax cross-entropy as one op (csrc/dense_xent.hip, ops/dense_xent.py):
+    # x, w, bias, labels, logits, lse, loss, M, N, K | gout, gout's stride, logits, lse, labels, x, w, dx, dw, db, M, N, K
+    "tony_dense_xent_fwd": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int64,
+                            c_int64, c_void_p],
+    "tony_dense_xent_bwd": [c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                            c_void_p, c_int64, c_int64, c_int64, c_void_p],
     "tony_x3_wgrad_mode": [c_int],
     "tony_dgrad_one_launch": [c_int],
     "tony_wgrad_pf": [c_int],
