@@ -16,7 +16,7 @@ takes that path: a missing kernel library is an error (``_lib.lib``).
 Forward is one launch (``tony_conv2_fwd``) that writes the pooled ``y`` and a uint8 ``idx``, the window position 0..3
 of each maximum (the first one in row-major order, torch's rule); an odd ``OH`` or ``OW`` is pooled with floor and
 the last conv row or column is never computed.  The full-resolution activation is never written.  Backward expands
-``(dy, y, idx)`` in LDS -- ``dy`` at position ``idx`` where ``y > 0``, zero elsewhere, so the gradient at
+``(dy, y, idx)`` in LDS -- ``dy`` at position ``idx`` unless ``y <= 0``, zero elsewhere, so the gradient at
 ``relu == 0`` is 0 -- in ``tony_conv2_dgrad`` (only if ``x`` requires grad) and ``tony_conv2_wgrad``, whose partials
 ``tony_conv2_fold`` adds in index order.  No atomics: the same inputs give the same bits.
 """

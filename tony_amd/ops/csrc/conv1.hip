@@ -18,7 +18,7 @@
 //             lanes of a half store 128 contiguous bytes of one channel plane.  ReLU on the accumulators.
 //   backward  D[channel][tap] = dY'[32 x L] . Xcol[L x K] reduced over the L = N * OH * OW pixels two per step, column
 //             k*k the sum of dY' (the bias gradient), columns past it unused.  dy and y are read coalesced (lanes along
-//             a channel plane), masked (dy' = y > 0 ? dy : 0, torch's convention at 0) and laid into LDS as
+//             a channel plane), masked (dy' = y <= 0 ? 0 : dy, torch's: 0 at 0, dy at a NaN) and laid into LDS as
 //             [channel][pixel] rows of odd stride, from which the lane-per-channel operand reads are conflict free.
 //             A workgroup reduces a fixed run of images -- the grid is a function of N alone -- its four waves
 //             taking the pixel pairs of every row in turn; their accumulators meet in LDS in wave order and ONE 32x32
@@ -145,7 +145,7 @@ __global__ __launch_bounds__(kThreads) void conv1_bwd_kernel(const float* __rest
 #pragma unroll
           for (int k = 0; k < 8; ++k) {
             const float d = dy[off + k * g.ohw], v = y[off + k * g.ohw];
-            dyt[(wave * 8 + k) * kDyStride + px] = v > 0.f ? d : 0.f;
+            dyt[(wave * 8 + k) * kDyStride + px] = !(v <= 0.f) ? d : 0.f;  // threshold_backward: a NaN y passes dy
           }
         }
         __syncthreads();

@@ -21,9 +21,9 @@
 //             elementwise over four registers of a lane; the 32 lanes of a half store contiguous floats (and bytes of
 //             idx) of one pooled channel plane.
 //   backward  D[channel][tap] = dY'[32 x L] . Xcol[L x K] over the L conv pixels, column k*k the sum of dY' (the bias
-//             gradient).  dY' -- dy of the pooled pixel at the window position idx names where y > 0, zero at the other
+//             gradient).  dY' -- dy of the pooled pixel at the window position idx names unless y <= 0, 0 at the other
 //             three positions and under a dropped odd row or column -- is formed in REGISTERS: dy, y and idx are read
-//             coalesced (lanes along a pooled channel plane), dy masked by y > 0 is laid into LDS as [channel][pooled
+//             coalesced (lanes along a pooled channel plane), dy masked by !(y <= 0) is laid in LDS as [channel][pooled
 //             pixel] rows of odd stride with idx as bytes beside it (row stride 4 * 33: the lane-per-channel byte
 //             reads hit 32 distinct banks too), and a step reads one (value, position) of two pooled pixels and issues
 //             FOUR MFMAs, A = the value where the position matches and 0 elsewhere, B = the patch at the tap plus
@@ -156,7 +156,7 @@ __global__ __launch_bounds__(kThreads) void conv1_pool_bwd_kernel(const float* _
                                                                   const int images) {
   constexpr int KK = KS * KS;
   __shared__ float xt[kPatchFloats];
-  __shared__ float dyt[kCout * kDyStride];       // [channel][pooled pixel]: y > 0 ? dy : 0
+  __shared__ float dyt[kCout * kDyStride];       // [channel][pooled pixel]: y <= 0 ? 0 : dy
   __shared__ uint8_t post[kCout * kIdxStride];   // [channel][pooled pixel]: idx
   __shared__ int xoff[kPoolPix];                 // [pooled pixel]: patch offset of its window's first conv pixel
   static_assert(kCout * kDyStride >= kWaves * kCout * 32, "the waves' accumulators meet in the dy tile's LDS");
@@ -186,7 +186,7 @@ __global__ __launch_bounds__(kThreads) void conv1_pool_bwd_kernel(const float* _
 #pragma unroll
           for (int k = 0; k < 8; ++k) {
             const float d = dy[off + k * g.phw], v = y[off + k * g.phw];
-            dyt[(wave * 8 + k) * kDyStride + px] = v > 0.f ? d : 0.f;
+            dyt[(wave * 8 + k) * kDyStride + px] = !(v <= 0.f) ? d : 0.f;  // threshold_backward: a NaN y passes dy
             post[(wave * 8 + k) * kIdxStride + px] = idx[off + k * g.phw];
           }
         }

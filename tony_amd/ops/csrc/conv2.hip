@@ -2,7 +2,7 @@
 // channels, k in {3, 5}, stride 1, padding 0 or (k - 1) / 2, a padded plane at most 64 wide, and its data, weight and
 // bias gradients.  Neither the full-resolution activation nor its gradient ever exists in memory: the forward writes
 // the pooled y and a uint8 idx (the window position 0..3 of the maximum, the first one in row-major order), the
-// backward expands (dy, y, idx) into dY' -- dy at position idx where y > 0, zeros elsewhere -- while staging it in LDS.
+// backward expands (dy, y, idx) into dY' -- dy at position idx unless y <= 0, zeros elsewhere -- while staging it.
 //
 // All three products run on v_mfma_f32_32x32x2_f32 (lane l, half h = l / 32: A[i = l % 32][k = h], B[k = h][j = l % 32],
 // accumulator r of lane l is D[8 * (r / 4) + 4 * h + r % 4][l % 32]), the im2col formed only in LDS addresses and the
@@ -87,8 +87,8 @@ __device__ __forceinline__ void stage_x(float* __restrict__ dst, int chs, const 
 }
 
 // NCO channel planes of dY' from co0, rows row0 .. + nrows and columns col0 .. + ncols of the CONV plane, as
-// dst[c * chs + r * ncols + col]: dy of the pooled pixel at the window position idx names if y > 0 (the gradient at
-// relu == 0 is 0), zeros at the other three positions, under an odd last row / column and outside the plane
+// dst[c * chs + r * ncols + col]: dy of the pooled pixel at the window position idx names unless y <= 0 (0 at relu ==
+// 0, dy at a NaN y), zeros at the other three positions, under an odd last row / column and outside the plane
 template <int NCO>
 __device__ __forceinline__ void stage_dyx(float* __restrict__ dst, int chs, const float* __restrict__ dy,
                                           const float* __restrict__ y, const uint8_t* __restrict__ idx, const Geo& g,
@@ -102,7 +102,7 @@ __device__ __forceinline__ void stage_dyx(float* __restrict__ dst, int chs, cons
     float v = 0.f;
     if (oh >= 0 && oh < 2 * g.PH && ow >= 0 && ow < 2 * g.PW) {
       const int64_t off = base + c * g.phw + static_cast<int64_t>(oh >> 1) * g.PW + (ow >> 1);
-      if (idx[off] == 2 * (oh & 1) + (ow & 1) && y[off] > 0.f) v = dy[off];
+      if (idx[off] == 2 * (oh & 1) + (ow & 1) && !(y[off] <= 0.f)) v = dy[off];  // threshold_backward: NaN passes
     }
     dst[c * chs + e] = v;
   }

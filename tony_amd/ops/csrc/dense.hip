@@ -1,5 +1,5 @@
 // Dense layers of the MNIST networks, fp32 in and out: y = x w^T + b (optionally ReLU) for x [M, K], w [N, K], b [N],
-// and its data, weight and bias gradients with ReLU's backward mask (y > 0) applied while dy is staged, so no masked
+// and its data, weight and bias gradients with ReLU's backward mask (not y <= 0) applied as dy is staged, so no masked
 // copy of dy ever exists in memory.  K % 4 == 0 (every row takes 16-byte loads); M and N are arbitrary, ragged tiles
 // are zero-filled on the way in and masked on the way out.  No atomics: every grid and every summation order is a
 // function of (M, N, K) alone, so the same inputs give the same bits.
@@ -182,13 +182,14 @@ __global__ __launch_bounds__(kThreads) void dense_fold_kernel(const float* __res
   y[i] = relu ? relu_f(v) : v;
 }
 
-// dy' at [m][n], zero outside the matrix; y == nullptr without ReLU.  NaN > 0 is false, as in torch's backward.
+// dy' at [m][n], zero outside the matrix; y == nullptr without ReLU.  The mask is torch's threshold_backward,
+// y <= 0 ? 0 : dy: NaN <= 0 is false, so the gradient passes through a NaN activation (y > 0 would drop it).
 __device__ __forceinline__ float masked_dy(const float* __restrict__ dy, const float* __restrict__ y, int m, int n,
                                            const Shape& g) {
   if (m >= g.M || n >= g.N) return 0.f;
   const int64_t off = static_cast<int64_t>(m) * g.N + n;
   const float v = dy[off];
-  return y == nullptr || y[off] > 0.f ? v : 0.f;
+  return y == nullptr || !(y[off] <= 0.f) ? v : 0.f;
 }
 
 __global__ __launch_bounds__(kThreads) void dense_dgrad_kernel(const float* __restrict__ dy, const float* __restrict__ y,
@@ -342,7 +343,7 @@ TONY_API int tony_dense_fold(const float* partials, const float* bias, float* y,
   return 0;
 }
 
-// dx[M,K] = dy' w with dy' = relu ? (y > 0 ? dy : 0) : dy; y may be null without relu.
+// dx[M,K] = dy' w with dy' = relu ? (y <= 0 ? 0 : dy) : dy; y may be null without relu.
 TONY_API int tony_dense_dgrad(const float* dy, const float* y, const float* w, float* dx, int64_t M, int64_t N,
                               int64_t K, int relu, hipStream_t stream) {
   if (dy == nullptr || w == nullptr || dx == nullptr || (relu && y == nullptr)) return -1;

@@ -15,7 +15,7 @@ takes that path: a missing kernel library is an error (``_lib.lib``).  The kerne
 
 Forward is ``tony_dense_fwd``; where the shape's long K is cut into ``S = tony_dense_splits(M, N, K) > 1`` slices it
 writes ``S`` partial products and ``tony_dense_fold`` adds them in index order, adds the bias and applies ReLU.  The
-forward saves ``(x, weight, y)``: ``y > 0`` is ReLU's backward mask, applied inside ``tony_dense_dgrad`` (only if ``x``
+forward saves ``(x, weight, y)``: ``not y <= 0`` is ReLU's backward mask, applied in ``tony_dense_dgrad`` (only if ``x``
 requires grad) and ``tony_dense_wgrad`` (``dw`` and ``db``) while ``dy`` is staged.  No atomics: the same inputs give
 the same bits.  ``ops.linear`` (bf16, with its fp32 vendor path for the image models' heads) is a different op and is
 untouched.
